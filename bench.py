@@ -36,6 +36,15 @@ Products-sized synthetic partition per GPU) as the secondary field "weak".
 Launch: `python bench.py --gpus N` starts N ranks itself (torch.distributed.run on
 127.0.0.1) unless it already runs under a launcher (WORLD_SIZE set, which must equal N).
 `--device cpu` runs the same code on the host-CPU backend with gloo (plumbing checks only).
+
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) does what the headline needs
+and no more: the graph, W warm-up steps, N timed steps, the result line.  `--full` adds
+everything else this file measures or checks: the fused step against the unfused chain, the
+SpMM's roofline and gather ceiling, the host-CPU baselines, the "gat", "rmat", "banded" and
+"weak" fields, and at N > 1 the per-aggregation kernel and exchange times.
+`--dump-outputs DIR` writes the arrays the last timed step produced (H1, H2, G1, G0; a fixed
+seeded sample of their rows) as DIR/<name>.npy, so two builds can be compared output for
+output: the graph and the inputs are seeded, the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -410,6 +419,28 @@ def make_fused_step(agg, X, dY, bufs):
     return step
 
 
+OUTPUT_NAMES = ("H1", "H2", "G1", "G0")   # the step's four aggregation outputs, in bufs order
+DUMP_BYTES = 60_000_000                    # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, bufs, rank=0, world=1):
+    """--dump-outputs: the step's outputs as they stand after the last timed step, float32,
+    as path/<name>.npy (N > 1: path/<name>_rank<r>.npy, the rank's own rows).  An output
+    too large for its share of DUMP_BYTES is written as a sample of its rows: the same rows
+    of every output in every run (seed 2024, ascending), so two runs compare row for row."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(OUTPUT_NAMES, bufs):
+        keep = DUMP_BYTES // (len(OUTPUT_NAMES) * world * 4 * t.shape[1])
+        if t.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(2024).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+    log(f"[bench] outputs written to {path}")
+
+
 def timed_steps(step, steps, warmup, sync, barrier, reduce_max):
     for _ in range(warmup):
         step()
@@ -575,21 +606,12 @@ def strong_family(args, kind, rank, world, dev, be, comm, timer, sync, barrier, 
     name = best.name
     t_step = timed_steps(make_step(best.agg, X, dY, bufs), args.steps if kind == "uniform" else max(args.steps // 2, 2),
                          args.warmup if kind == "uniform" else 2, sync, barrier, reduce_max)
-    t_kernel, alg = best.kernel(timer)
-    t_ex = best.exchange(timer) if world > 1 else 0.0
+    if kind == "uniform" and args.dump_outputs:
+        dump_outputs(args.dump_outputs, bufs, rank, world)
     out = {"value": 4 * g.nnz / t_step, "ms_per_step": t_step * 1e3, "real_data": real,
-           "roofline": {"bound": "hbm", "achieved": alg / t_kernel / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                        "frac": alg / t_kernel / HBM_PEAK, "traffic": None,
-                        "kernel": f"gala::k_spmm_rowgroup (rank 0's SpMM launches of mode {best.name})",
-                        "kernel_ms": t_kernel * 1e3, "alg_bytes_per_launch": alg},
            "comm": {"mode": best.name, "backend": dist_backend(),
                     "candidates_ms_per_step": {k: v * 1e3 for k, v in cand.items()},
                     "halo_bytes_per_aggregation_per_rank": best.agg.halo_bytes(),
-                    "exchange_ms_per_aggregation": t_ex * 1e3,
-                    # the link rate the exchange achieved: this rank's exchanged bytes over the
-                    # time of one aggregation's collectives alone (xGMI under RCCL)
-                    "exchange_GBps_per_rank": (best.agg.halo_bytes() / t_ex / 1e9) if t_ex > 0 else None,
-                    "spmm_ms_per_aggregation": t_kernel * 1e3,
                     "halo_layout": pt1.halo_mode, "halo_rows_rank0": pt1.n_halo_rows,
                     "vcut_touched_fraction": frac,
                     "failed_candidates": failed,
@@ -597,6 +619,19 @@ def strong_family(args, kind, rank, world, dev, be, comm, timer, sync, barrier, 
                             "Exchange time is the collective(s) of one aggregation alone; it overlaps the SpMM "
                             "in the -overlap/-pipe modes. vcut-sparse: DCSR partial rows (only rows with a held "
                             "edge) sent by all-to-all, timed when the touched fraction is below 0.9."}}
+    if args.full:   # the chosen layout's SpMM and exchange, each timed alone
+        t_kernel, alg = best.kernel(timer)
+        t_ex = best.exchange(timer) if world > 1 else 0.0
+        out["roofline"] = {"bound": "hbm", "achieved": alg / t_kernel / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                           "frac": alg / t_kernel / HBM_PEAK, "traffic": None,
+                           "kernel": f"gala::k_spmm_rowgroup (rank 0's SpMM launches of mode {best.name})",
+                           "kernel_ms": t_kernel * 1e3, "alg_bytes_per_launch": alg}
+        out["comm"].update({
+            "exchange_ms_per_aggregation": t_ex * 1e3,
+            # the link rate the exchange achieved: this rank's exchanged bytes over the
+            # time of one aggregation's collectives alone (xGMI under RCCL)
+            "exchange_GBps_per_rank": (best.agg.halo_bytes() / t_ex / 1e9) if t_ex > 0 else None,
+            "spmm_ms_per_aggregation": t_kernel * 1e3})
     if comm.rccl:
         out["comm"]["rccl_note"] = "RCCL collectives over the node's GPUs"
     else:
@@ -651,7 +686,7 @@ def run_multi(args, rank, world, dev, be, timer, sync):
                    "n_vertices": g.n_rows, "edges": g.nnz, "F": F,
                    "parallelism": f"{fam['comm']['mode']} x{world} (RCCL)" if comm.rccl
                    else f"{fam['comm']['mode']} x{world} ({dist.get_backend()})"},
-        "roofline": fam["roofline"],
+        **({"roofline": fam["roofline"]} if args.full else {}),
         "comm": fam["comm"],
     }
     # secondary fields, each only while the budget holds; estimates from the uniform family's
@@ -823,29 +858,20 @@ def run_single(args, dev, be, timer, sync):
     dY = torch.rand((hg.n_rows, F), device=dev, generator=gen) * 2 - 1
     bufs = [be.empty(hg.n_rows, F) for _ in range(4)]
     ident = lambda x: x  # noqa: E731
-    # the fused step's outputs against the unfused chain's, once, outside the timed region
-    make_step(agg, X, dY, bufs)()
-    want = [b.clone() for b in bufs]
-    make_fused_step(agg, X, dY, bufs)()
-    fused_same = all(bool(torch.equal(a, b)) for a, b in zip(want, bufs))
-    del want
-    if not fused_same:
-        raise RuntimeError("bench.py: the fused step's outputs differ from the degree + ROW_BROADCAST + SpMM chain")
+    fused_same = None
+    if args.full:
+        # the fused step's outputs against the unfused chain's, once, outside the timed region
+        make_step(agg, X, dY, bufs)()
+        want = [b.clone() for b in bufs]
+        make_fused_step(agg, X, dY, bufs)()
+        fused_same = all(bool(torch.equal(a, b)) for a, b in zip(want, bufs))
+        del want
+        if not fused_same:
+            raise RuntimeError("bench.py: the fused step's outputs differ from the degree + ROW_BROADCAST + SpMM chain")
     t_step = timed_steps(make_fused_step(agg, X, dY, bufs), args.steps, args.warmup, sync, lambda: None, ident)
     value = 4 * hg.nnz / t_step
-    Y = bufs[0]
-    # the kernel and (HIP) the same-process gather probe, interleaved over three rounds
-    # (medians; both move with the GPU's load state, DESIGN §4.4)
-    k_rounds, c_rounds = [], []
-    for _ in range(3):
-        k_rounds.append(timer(lambda: be.spmm(agg.g, agg.Xs, Y, agg.norm, False), 10))
-        t_c = gather_ceiling(agg.g.col, agg.Xs, timer) if be.name == "hip" else None
-        if t_c:
-            c_rounds.append(t_c)
-    t_kernel = sorted(k_rounds)[1]
-    alg = spmm_alg_bytes(hg.n_rows, hg.n_rows, hg.nnz, F)
-    achieved = alg / t_kernel
-    gather_bytes = 4 * (hg.n_rows + 1) + hg.nnz * (4 + 4 * F) + 4 * hg.n_rows * F
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bufs)
     out = {
         "metric": "aggregated edges/sec, GCN-2 ogbn-products (4 F=32 aggregations per step)",
         "value": value,
@@ -863,10 +889,28 @@ def run_single(args, dev, be, timer, sync):
         "config": {"workload": "GCN-2 ogbn-products-shaped hot path: degree + 2 fwd + 2 bwd norm-scaled "
                                "SpMM aggregations, F=32",
                    "step": "degree norm and the next aggregation's ROW_BROADCAST folded into the SpMM "
-                           "epilogues (gala_spmm_ex_f32 / gala_row_broadcast_deg_f32); outputs checked "
-                           "bit-identical to the unfused chain in this run",
+                           "epilogues (gala_spmm_ex_f32 / gala_row_broadcast_deg_f32)" +
+                           ("; outputs checked bit-identical to the unfused chain in this run" if args.full else
+                            "; --full checks the outputs bit-identical to the unfused chain"),
                    "fused_step_bit_identical": fused_same,
                    "n_vertices": hg.n_rows, "edges": hg.nnz, "F": F, "parallelism": "1 GPU"},
+    }
+    if not args.full:
+        return out
+    Y = bufs[0]
+    # the kernel and (HIP) the same-process gather probe, interleaved over three rounds
+    # (medians; both move with the GPU's load state, DESIGN §4.4)
+    k_rounds, c_rounds = [], []
+    for _ in range(3):
+        k_rounds.append(timer(lambda: be.spmm(agg.g, agg.Xs, Y, agg.norm, False), 10))
+        t_c = gather_ceiling(agg.g.col, agg.Xs, timer) if be.name == "hip" else None
+        if t_c:
+            c_rounds.append(t_c)
+    t_kernel = sorted(k_rounds)[1]
+    alg = spmm_alg_bytes(hg.n_rows, hg.n_rows, hg.nnz, F)
+    achieved = alg / t_kernel
+    gather_bytes = 4 * (hg.n_rows + 1) + hg.nnz * (4 + 4 * F) + 4 * hg.n_rows * F
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK,
                      "traffic": load_traffic("k_spmm_rowgroup<4, 8, 1, 4, false, false, false, false>") if be.name == "hip" else None,
@@ -876,7 +920,7 @@ def run_single(args, dev, be, timer, sync):
                      "traffic_note": "PMC FETCH_SIZE*2+WRITE_SIZE per launch (profiles/traffic.json, null when the kernel's "
                                      "sources changed since that pass); "
                                      "uniform random columns: each edge's 128-B X row misses L2"},
-    }
+    })
     with_traffic_rate(out["roofline"])
     if c_rounds:
         t_ceil = sorted(c_rounds)[len(c_rounds) // 2]
@@ -1182,7 +1226,19 @@ def main():
     ap.add_argument("--data", help="dataset directory in the reference's npy format (Adj_src.npy, Adj_dst.npy) "
                                    "or a Matrix Market .mtx graph; default: Data/Products/ when present, else "
                                    "the synthetic graph")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the fused step checked against the unfused chain, "
+                         "roofline and gather-ceiling kernel timings, host-CPU baselines, the gat / rmat / banded / "
+                         "weak fields (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (H1, H2, G1, G0; float32, a fixed "
+                         "seeded sample of their rows, at most 60 MB in all) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the headline's steps alone
+        args.no_cpu_baseline = args.no_rmat = args.no_banded = args.no_gat = args.no_weak = True
+        args.banded = False
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))

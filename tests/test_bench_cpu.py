@@ -35,7 +35,7 @@ def _json_lines(out: str):
 
 def test_bench_self_launches_ranks():
     r = _run_ranks(["--gpus", "2", "--device", "cpu", "--scale", "0.002", "--steps", "2", "--warmup", "1",
-                    "--calib-steps", "1"], _env())
+                    "--calib-steps", "1", "--full"], _env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout                 # rank 0 only
@@ -80,7 +80,7 @@ def test_bench_eight_ranks():
     env = _env()
     env["OMP_NUM_THREADS"] = "1"
     r = _run_ranks(["--gpus", "8", "--device", "cpu", "--scale", "0.002", "--steps", "2", "--warmup", "1",
-                    "--calib-steps", "1"], env)
+                    "--calib-steps", "1", "--full"], env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout
@@ -96,7 +96,7 @@ def test_bench_budget_keeps_the_headline():
     (its first candidate timed, the others and every secondary field skipped, agreed over
     the ranks), with the skips listed under budget.skipped_for_time."""
     r = _run_ranks(["--gpus", "2", "--device", "cpu", "--scale", "0.002", "--steps", "2", "--warmup", "1",
-                    "--calib-steps", "1", "--budget-s", "0.01"], _env())
+                    "--calib-steps", "1", "--budget-s", "0.01", "--full"], _env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout
@@ -114,7 +114,7 @@ def test_bench_budget_keeps_the_headline():
 
 def test_bench_single_rank_line():
     r = subprocess.run([sys.executable, BENCH, "--device", "cpu", "--scale", "0.002", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--banded"],
+                        "--warmup", "1", "--no-cpu-baseline", "--banded", "--full"],
                        capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     (d,) = _json_lines(r.stdout)
@@ -195,6 +195,54 @@ def test_bench_matrix_market_graph(tmp_path):
     (d,) = _json_lines(res.stdout)
     assert d["config"]["n_vertices"] == n and d["config"]["edges"] == g.nnz
     assert "Matrix Market" in d["data"]
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path, monkeypatch):
+    """Without --full the line carries the headline and none of the secondary measurements;
+    --dump-outputs writes the last timed step's four outputs as float32 .npy files, equal to
+    the oracle's chain on the same seeded graph and inputs, and the same from run to run.  An
+    output over its share of the byte cap is written as the same seeded rows every time."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import bench
+    import oracle as orc
+    outs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--device", "cpu", "--scale", "0.002", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        (d,) = _json_lines(r.stdout)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "edges/s" and d["dtype"] == "f32"
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 / (4 * d["config"]["edges"]) - 1) < 1e-9
+        assert not any(k in d for k in ("roofline", "cpu_baseline", "gat", "rmat", "banded", "weak"))
+        assert sorted(os.listdir(tmp_path / name)) == ["G0.npy", "G1.npy", "H1.npy", "H2.npy"]
+        outs.append({k: np.load(tmp_path / name / f"{k}.npy") for k in bench.OUTPUT_NAMES})
+    n = d["config"]["n_vertices"]
+    for k in bench.OUTPUT_NAMES:
+        assert outs[0][k].dtype == np.float32 and outs[0][k].shape == (n, 32)
+        np.testing.assert_array_equal(outs[0][k], outs[1][k])
+    # the same graph and inputs, through the oracle's degree-normed chain
+    g = bench.products_graph("uniform", 0.002)
+    gen = torch.Generator().manual_seed(1234)
+    X = (torch.rand((n, 32), generator=gen) * 2 - 1).numpy()
+    dY = (torch.rand((n, 32), generator=gen) * 2 - 1).numpy()
+    og = orc.Graph(g.n_rows, g.n_cols, g.rowptr, g.col)
+    norm = (np.diff(g.rowptr).astype(np.float32) ** np.float32(-0.5)).astype(np.float32)
+    agg = lambda H: orc.spmm(og, H, src_scale=norm, dst_scale=norm)  # noqa: E731
+    H1 = agg(X)
+    G1 = agg(dY)
+    for k, want in zip(bench.OUTPUT_NAMES, (H1, agg(H1), G1, agg(G1))):
+        np.testing.assert_allclose(outs[0][k], want, rtol=1e-5, atol=1e-6)
+    # over the cap: the same ascending seeded rows of every output
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 4 * 32 * 100)
+    bufs = [torch.from_numpy(outs[0][k]) for k in bench.OUTPUT_NAMES]
+    bench.dump_outputs(str(tmp_path / "c"), bufs)
+    idx = np.sort(np.random.default_rng(2024).choice(n, 100, replace=False))
+    for k in bench.OUTPUT_NAMES:
+        np.testing.assert_array_equal(np.load(tmp_path / "c" / f"{k}.npy"), outs[0][k][idx])
 
 
 

@@ -255,7 +255,7 @@ def test_bench_partitioned_path_over_rccl_one_rank():
                                                             "MASTER_PORT", "GALA_DIST_BACKEND")}
     env["GALA_BENCH_DIST"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.05", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=200, env=env, cwd=root)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=200, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-4000:]
     (d,) = [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and d["comm"]["backend"] == "nccl"
@@ -371,7 +371,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu_gloo():
                                                             "MASTER_PORT")}
     env["GALA_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--scale", "0.02", "--steps",
-                        "2", "--warmup", "1", "--no-weak"], capture_output=True, text=True, timeout=220, env=env,
+                        "2", "--warmup", "1", "--no-weak", "--full"], capture_output=True, text=True, timeout=220, env=env,
                        cwd=root)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -6,10 +6,10 @@
 #   tests            python -m pytest tests -m gpu            -> gpurun_out/pytest_gpu.log
 #   tests=EXPR       ... -k EXPR ("_or_" stands for " or ")
 #   smoke            __graft_entry__.smoke()                -> gpurun_out/smoke.log
-#   bench            python bench.py (N = 1 defaults)        -> gpurun_out/bench.json (+ .log)
+#   bench            python bench.py --full (N = 1 defaults) -> bench.json (+ .log) in the output folder
 #   bench=ARGS       python bench.py ARGS (spaces as commas)
-#   benchdist        GALA_BENCH_DIST=1 bench.py: the strong-scaling path over RCCL at world 1
-#                                                            -> gpurun_out/bench_dist.json
+#   benchdist        GALA_BENCH_DIST=1 bench.py --full: the strong-scaling path over RCCL at
+#                    world 1                                 -> bench_dist.json in the output folder
 #   prof             rocprofv3 --kernel-trace --stats of bench.py -> gpurun_out/prof_stats/
 #   pmc              FETCH_SIZE and WRITE_SIZE passes (one --pmc run each) of bench.py, then
 #                    tools/pmc_traffic.py                   -> gpurun_out/traffic.json
@@ -27,13 +27,13 @@ OUT="$GRAFT_REPO_ROOT/gpurun_out"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 export PYTHONPATH="$GRAFT_REPO_ROOT/gala-gnn-acceleration-language_amd${PYTHONPATH:+:$PYTHONPATH}"
-BENCH_PROF_ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-banded --no-rmat"
+BENCH_PROF_ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-banded --no-rmat"
 # the banded and R-MAT families' SpMMs run the uniform one's row kernel: rocprof and PMC runs
 # of bench.py leave them out, so a kernel's average / bytes are the headline graph's (the
 # families' own: pmccmd=banded,python3,<repo>/tools/banded_spmm.py,banded and
 # pmccmd=rmat,python3,<repo>/tools/rmat_prof.py, merged into profiles/traffic.json under a
 # "banded|" / "rmat|" prefix by tools/merge_traffic.py)
-BENCH_PMC_ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-banded --no-rmat"
+BENCH_PMC_ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-banded --no-rmat"
 
 step() {  # name, limit, command...
     local name=$1 lim=$2
@@ -61,7 +61,7 @@ for s in "$@"; do
             || { tail -30 "$OUT/smoke.log"; exit 1; }
         tail -1 "$OUT/smoke.log" ;;
     bench)
-        step bench 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -30 "$OUT/bench.log"; exit 1; }
+        step bench 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -30 "$OUT/bench.log"; exit 1; }
         cat "$OUT/bench.json" ;;
     bench=*)
         a="${s#bench=}"
@@ -69,7 +69,7 @@ for s in "$@"; do
         cat "$OUT/bench.json" ;;
     benchdist)
         # the partitioned path on this one GPU (RCCL at world 1: the collectives run)
-        GALA_BENCH_DIST=1 step benchdist 900 python -u bench.py --no-cpu-baseline > "$OUT/bench_dist.json" \
+        GALA_BENCH_DIST=1 step benchdist 900 python -u bench.py --full --no-cpu-baseline > "$OUT/bench_dist.json" \
             2> "$OUT/bench_dist.log" || { tail -30 "$OUT/bench_dist.log"; exit 1; }
         cat "$OUT/bench_dist.json" ;;
     prof)
