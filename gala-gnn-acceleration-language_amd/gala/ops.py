@@ -572,23 +572,32 @@ def gat_in_prep(X, u, c, heads, xext=None):
     return xext
 
 
-def gat_in_fwd(g: DeviceGraph, xext, W, b, heads, fin, slope=0.2, order=None, relu=False, T=None):
+def gat_in_fwd(g: DeviceGraph, xext, W, b, heads, fin, slope=0.2, order=None, relu=False, T=None, Y=None, Ym=None):
     """gala_gat_in_fwd_f32: (Y, Ym, q, sma); writes q into xext.  order: int32 row order.
     T ([N, 896], symmetric g only): gala_gat_in_fwd_t_f32, which also forms the backward's
-    per-column aggregates there."""
+    per-column aggregates there.  Y, Ym (optional outputs): [N, H*D] with unit column stride
+    and one row stride, e.g. column views of wider buffers; W likewise (ldw = W.stride(0))."""
     F = W.shape[0]
     D = F // heads
-    Y = torch.empty(g.n_rows, F, device=W.device, dtype=torch.float32)
-    Ym = torch.empty_like(Y)
+    if Y is None:
+        Y = torch.empty(g.n_rows, F, device=W.device, dtype=torch.float32)
+    if Ym is None:
+        Ym = torch.empty_strided(Y.shape, Y.stride(), device=W.device, dtype=torch.float32)
+    for name, t in (("Y", Y), ("Ym", Ym)):
+        if tuple(t.shape) != (g.n_rows, F) or t.dtype != torch.float32 or (F > 1 and t.stride(1) != 1):
+            raise ValueError(f"gat_in_fwd: {name} must be float32 [{g.n_rows}, {F}] with unit column stride")
+    if Ym.stride(0) != Y.stride(0) or (fin > 1 and W.stride(1) != 1):
+        raise ValueError("gat_in_fwd: Y and Ym share one row stride; W has unit column stride")
+    ldy = max(Y.stride(0), F)  # (empty tensors report any stride)
     q = torch.empty(g.n_rows, heads, device=W.device, dtype=torch.float32)
     sma = torch.empty_like(q)
     flags = _abi.GALA_GAT_IN_RELU if relu else 0
     if T is None:
         _abi.call("gala_gat_in_fwd_f32", g.csr(0), _dp(order), fin, heads, D, slope, _dp(xext), _dp(W), W.stride(0),
-                  _dp(b), _dp(Y), _dp(Ym), F, _dp(q), _dp(sma), flags, _stream())
+                  _dp(b), _dp(Y), _dp(Ym), ldy, _dp(q), _dp(sma), flags, _stream())
     else:
         _abi.call("gala_gat_in_fwd_t_f32", g.csr(0), _dp(order), fin, heads, D, slope, _dp(xext), _dp(W),
-                  W.stride(0), _dp(b), _dp(Y), _dp(Ym), F, _dp(q), _dp(sma), flags, _dp(T), _stream())
+                  W.stride(0), _dp(b), _dp(Y), _dp(Ym), ldy, _dp(q), _dp(sma), flags, _dp(T), _stream())
     return Y, Ym, q, sma
 
 
@@ -598,6 +607,10 @@ def gat_in_bwd(gT: DeviceGraph, xext, dY, Y, Ym, sma, heads, fin, slope=0.2, ord
     F = dY.shape[1]
     D = F // heads
     n = dY.shape[0]
+    # dY, Y, Ym: one row stride (ldy, a multiple of 4 floats for the kernel's float4 loads)
+    if not (dY.stride(0) == Y.stride(0) == Ym.stride(0)) or (F > 1 and not (dY.stride(1) == Y.stride(1) == Ym.stride(1) == 1)):
+        raise ValueError("gat_in_bwd: dY, Y and Ym share one row stride and have unit column stride")
+    ldy = max(dY.stride(0), F)
     daL = torch.empty(n, heads, device=dY.device, dtype=torch.float32)
     M = torch.empty(heads, D, fin + 1, device=dY.device, dtype=torch.float32)
     wsb = _abi.lib().gala_gat_in_bwd_workspace(heads)
@@ -605,9 +618,9 @@ def gat_in_bwd(gT: DeviceGraph, xext, dY, Y, Ym, sma, heads, fin, slope=0.2, ord
     flags = _abi.GALA_GAT_IN_RELU if relu else 0
     if T is None:
         _abi.call("gala_gat_in_bwd_f32", gT.csr(0), _dp(order), fin, heads, D, slope, _dp(xext), _dp(dY), _dp(Y),
-                  _dp(Ym), F, _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
+                  _dp(Ym), ldy, _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
     else:
-        _abi.call("gala_gat_in_bwd_t_f32", n, _dp(order), fin, heads, D, _dp(T), _dp(dY), _dp(Y), _dp(Ym), F,
+        _abi.call("gala_gat_in_bwd_t_f32", n, _dp(order), fin, heads, D, _dp(T), _dp(dY), _dp(Y), _dp(Ym), ldy,
                   _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
     return daL, M
 
@@ -620,12 +633,33 @@ def degree_order(rowptr):
     return order
 
 
+def pattern_is_symmetric(g: DeviceGraph) -> bool:
+    """Whether g's CSR equals its transpose's (gala_host_csr_transpose on a host copy; kept on g)."""
+    sym = getattr(g, "_symmetric", None)
+    if sym is None:
+        sym = False
+        if g.n_seg == 1 and g.n_rows == g.n_cols:
+            rp = np.ascontiguousarray(g.rowptr.cpu().numpy(), np.int32)
+            col = np.ascontiguousarray(g.col.cpu().numpy(), np.int32)
+            trp, tcol, perm = np.empty_like(rp), np.empty_like(col), np.empty_like(col)
+            _abi.call("gala_host_csr_transpose", g.n_rows, g.n_cols, rp.ctypes.data, col.ctypes.data,
+                      trp.ctypes.data, tcol.ctypes.data, perm.ctypes.data)
+            sym = bool(np.array_equal(trp, rp) and np.array_equal(tcol, col))
+        g._symmetric = sym
+    return sym
+
+
 def gat_input_layer(g: DeviceGraph, X, W, b, wL, bL, wR, bR, heads, slope=0.2, dY=None, gT=None, order=None,
-                    order_t=None, relu=False, tmode=False):
+                    order_t=None, relu=False, tmode=False, Y=None, Ym=None):
     """Config 3's layer 1 in input space through the C ABI, the composition of the mirror's
     GatInputLayer: forward (Y, q, sma, xext) and, with dY, the gradients
     {W, b, wL, bL, wR, bR} (REF: d aR = d aL) and d_aL.  gT: the transposed pattern (default g,
-    the symmetric graph of an undirected program)."""
+    the symmetric graph of an undirected program).  tmode without gT needs a symmetric g
+    (checked on the host once per graph, as the mirror's transposed_pattern does): ValueError
+    otherwise, before any launch.  Y, Ym: optional outputs (gat_in_fwd)."""
+    if tmode and gT is None and not pattern_is_symmetric(g):
+        raise ValueError("gat_input_layer: tmode without gT needs a symmetric pattern (the backward's aggregates "
+                         "are formed over g itself); pass gT, the transposed pattern, for the walk")
     F, fin = W.shape
     H, D = heads, F // heads
     u, c = gat_in_compose(W, b, wL, bL, wR, bR, heads)
@@ -633,7 +667,7 @@ def gat_input_layer(g: DeviceGraph, X, W, b, wL, bL, wR, bR, heads, slope=0.2, d
     # T mode (tmode, the symmetric g of an undirected program: gT None): the forward also forms
     # the backward's per-column aggregates
     T = torch.empty(g.n_rows, 896, device=X.device, dtype=torch.float32) if tmode and gT is None else None
-    Y, Ym, q, sma = gat_in_fwd(g, xext, W, b, heads, fin, slope, order=order, relu=relu, T=T)
+    Y, Ym, q, sma = gat_in_fwd(g, xext, W, b, heads, fin, slope, order=order, relu=relu, T=T, Y=Y, Ym=Ym)
     out = {"Y": Y, "Ym": Ym, "q": q, "sma": sma, "xext": xext, "T": T}
     if dY is None:
         return out

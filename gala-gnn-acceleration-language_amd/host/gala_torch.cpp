@@ -1564,6 +1564,9 @@ struct GatInputLayer : public torch::autograd::Function<GatInputLayer> {
         auto dY = grad_outputs[0].contiguous();
         check_dev(dY, torch::kFloat, "grad");
         check_on(dY, x, "grad");
+        // the backward reads dY rows as float4: a contiguous grad at a storage offset that is
+        // not 16-byte aligned (a view into a larger buffer) is copied to a fresh allocation
+        if (reinterpret_cast<uintptr_t>(dY.data_ptr<float>()) & 15) dY = dY.clone();
         // the reference's REF backward on the undirected graph is dX = A_alpha dY over A itself;
         // regrouped by column it walks A's transposed pattern (A's own tensors when symmetric)
         const PatternT &pt = transposed_pattern(2 * li);

@@ -447,7 +447,8 @@ def gat_input_layer_ref(rowptr, col, X, W, b, wL, bL, wR, bR, dY, heads, slope=0
     sits at 0 may take the other LeakyReLU slope under a one-ulp change and move its row's
     d_aL by ~ alpha * |d alpha|; the tests check the logits themselves
     against the float64 Linear separately.
-    Returns a dict of numpy arrays (Y, daL, aR, dW, db, dwL, dbL, dwR, dbR, v1)."""
+    Returns a dict of numpy arrays (Y, daL, aR, dW, db, dwL, dbL, dwR, dbR, v1, and the terms
+    the gradients sum: dX = dX_agg [n, F] and the assembled dv1 [n, F] in float64)."""
     X = np.ascontiguousarray(X, np.float32)
     F, fin = W.shape
     H, D = heads, F // heads
@@ -467,4 +468,4 @@ def gat_input_layer_ref(rowptr, col, X, W, b, wL, bL, wR, bR, dY, heads, slope=0
     db = dv1.sum(0)
     dw = np.einsum("rh,rhd->hd", daL, v1.astype(np.float64).reshape(n, H, D)).reshape(-1)
     return dict(Y=lay.Y, daL=lay.daL, aR=lay.aR, q=lay.q, dW=dW, db=db, dwL=dw, dbL=daL.sum(0), dwR=dw,
-                dbR=daL.sum(0), v1=v1)
+                dbR=daL.sum(0), v1=v1, dX=lay.dX, dv1=dv1)

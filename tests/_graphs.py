@@ -56,6 +56,98 @@ def long_row_graph(seed=3) -> layout.HostGraph:
     return layout.csr_build(n, n, src, dst)
 
 
+PHASE_N = 8205          # 1026 blocks of 8 rows on a grid of 512: workgroups 0, 1 run three phases
+PHASE_STEP = 8 * 512    # with the identity order row r hands off to row r + PHASE_STEP
+PHASE_S = (0, 1, 16, 17, 64, 65)
+PHASE_SPECIAL = (3, 15, 31, 32, 33, 63, 127, 128, 129)
+PHASE_CLASSES = ((0, 0), (1, 15), (16, 16), (17, 63), (64, 64), (65, 1 << 30))
+
+
+def phase_class(deg):
+    """Batch class of a degree: 0, 1-15, 16, 17-63, 64, >= 65 (the 16-edge batch and the
+    64-index column window of gat_input.hip's row walk)."""
+    deg = np.asarray(deg)
+    out = np.full(deg.shape, -1, np.int64)
+    for k, (lo, hi) in enumerate(PHASE_CLASSES):
+        out[(deg >= lo) & (deg <= hi)] = k
+    return out
+
+
+def phase_degrees(rng) -> np.ndarray:
+    """The prescribed degrees of phase_graph (see there)."""
+    n, step = PHASE_N, PHASE_STEP
+    deg = rng.integers(0, 13, n)                         # every other row: ~6 on average
+    deg[3000:3050] = 0                                   # blocks of empty rows in both phases
+    deg[7000:7050] = 0
+    for i in range(72):                                  # every ordered pair of S, twice, over
+        r = 56 * i + i % 8                               # workgroups 0, 7, 14, ... and all 8 wave slots
+        deg[r], deg[r + step] = PHASE_S[i % 6], PHASE_S[(i // 6) % 6]
+    # the third phase (workgroups 0 and 1: rows 8192..8204) and the rows handing off to it;
+    # slots 5..7 of workgroup 1 (rows 4109..4111) hand off to no row
+    deg[2 * step:] = [65, 0, 17, 64, 1, 16, 129, 3, 0, 64, 17, 1, 65]
+    deg[step + 8:step + 16] = [16, 65, 0, 1, 64, 65, 17, 0]
+    # rows at the batch and window edges, as first-phase rows and as rows handed off to
+    for k, d in enumerate(PHASE_SPECIAL):
+        deg[1001 + 104 * k] = d
+        deg[step + 1003 + 104 * k] = d
+    deg[2000], deg[2000 + step] = 129, 128               # window refresh on both sides of a hand-off
+    deg[1905 + step] = 1024                              # the longest row below the hub-row threshold
+    return deg
+
+
+def phase_graph(symmetric: bool, seed=11) -> layout.HostGraph:
+    """8205 rows for the persistent input-space GAT kernels (csrc/gat_input.hip: 8 rows per
+    workgroup phase, at most 512 workgroups): every workgroup runs two phases, workgroups 0 and
+    1 three, the last block has 5 rows.  With the identity order row r hands off to row r +
+    4096; the degrees are prescribed so that every ordered pair of {0, 1, 16, 17, 64, 65} is
+    such a hand-off, beside rows of exactly 3, 15, 31, 32, 33, 63, 127, 128, 129 and 1024
+    edges, blocks of empty rows and small random rows (0..12 edges).
+    Directed: columns drawn uniformly, duplicates kept.  Symmetric: the same degrees kept
+    exactly -- row r repeated deg[r] times, the list shuffled and consecutive entries (u, v)
+    joined as the edges u -> v and v -> u (a loop (u, u) stored twice) -- so its empty rows are
+    isolated vertices.  check_phase_graph asserts what the tests rely on."""
+    rng = np.random.default_rng(seed)
+    deg = phase_degrees(rng)
+    n = PHASE_N
+    if not symmetric:
+        src = np.repeat(np.arange(n), deg)
+        dst = rng.integers(0, n, src.shape[0])
+    else:
+        if deg.sum() % 2:
+            deg[5] += 1                                  # (a small random row)
+        stubs = rng.permutation(np.repeat(np.arange(n), deg))
+        u, v = stubs[0::2], stubs[1::2]
+        src, dst = np.concatenate([u, v]), np.concatenate([v, u])
+        o = np.lexsort((dst, src))                       # rows sorted by column: A^T's CSR is A's
+        src, dst = src[o], dst[o]
+    return layout.csr_build(n, n, src.astype(np.int32), dst.astype(np.int32))
+
+
+def check_phase_graph(g: layout.HostGraph, symmetric: bool):
+    """What the multi-phase tests rely on, from the built rowptr."""
+    n, step = g.n_rows, PHASE_STEP
+    deg = np.diff(g.rowptr.astype(np.int64))
+    assert n == PHASE_N and n % 8 != 0 and n > 2 * step and (n + 7) // 8 == 1026
+    cls = phase_class(deg)
+    assert (cls >= 0).all()
+    pairs = set(zip(cls[:n - step].tolist(), cls[step:].tolist()))
+    missing = [(a, b) for a in range(6) for b in range(6) if (a, b) not in pairs]
+    assert not missing, f"hand-off class pairs missing: {missing}"
+    third = set(zip(cls[step:n - step].tolist(), cls[2 * step:].tolist()))
+    assert len(third) >= 6, third                        # second -> third phase hand-offs differ
+    assert (deg >= 129).any() and deg.max() == 1024      # window refreshes; no hub-row plan (> 1024)
+    assert layout.split_threshold(n, g.nnz) == 1024
+    assert (deg == 0).sum() >= 100 and (deg[step:] == 0).any() and (deg[:step] == 0).any()
+    for d in PHASE_SPECIAL + (1024,):
+        assert (deg == d).any(), d
+    assert g.nnz < 150_000
+    gT, _ = layout.transpose(g)
+    same = np.array_equal(gT.rowptr, g.rowptr) and np.array_equal(gT.col, g.col)
+    assert same == symmetric
+    if symmetric:                                        # the empty rows are isolated
+        assert not np.isin(g.col, np.flatnonzero(deg == 0)).any()
+
+
 def features(n, F, seed=1234, integer=False):
     rng = np.random.default_rng(seed)
     if integer:

@@ -122,6 +122,14 @@ def test_mirror_op_equals_the_three_op_chain(E, symmetric):
     if symmetric:
         src = np.repeat(np.arange(g.n_rows, dtype=np.int32), np.diff(g.rowptr))
         g = layout.csr_build(g.n_rows, g.n_rows, np.concatenate([src, g.col]), np.concatenate([g.col, src]))
+    mirror_op_against_the_chain(E, g)
+
+
+def mirror_op_against_the_chain(E, g, pin_relu_mask=False):
+    """test_mirror_op_equals_the_three_op_chain's body on graph g.  pin_relu_mask: the chain's
+    ReLU takes the op's own mask (Y > 0), as ref_on_own_logits does for the oracle: the two
+    forwards differ by rounding, so among millions of outputs a few within an ulp of 0 land on
+    the other side of the kink and move a weight gradient by a whole alpha * dY * x term."""
     E.slots_clear()
     off, cols = dev(g.rowptr), dev(g.col)
     vals = torch.ones(g.nnz, device="cuda")
@@ -143,7 +151,13 @@ def test_mirror_op_equals_the_three_op_chain(E, symmetric):
         v1 = E.ffn_apply(x, params[0], params[1])
         aL = E.head_attn_apply(v1, params[2], params[3])
         Y0 = E.gat_aggregate_ffn_apply(aL, v1, params[4], params[5], 0, 0.2, 0)
-        if relu:
+        if relu and pin_relu_mask:
+            keep = Y.detach() > 0
+            flipped = keep != (Y0.detach() > 0)
+            print(f"relu mask: {int(flipped.sum())} of {flipped.numel()} outputs on the other side of 0, "
+                  f"largest |Y| among them {float(Y0.detach()[flipped].abs().max()) if flipped.any() else 0.0:.3g}")
+            Y0 = Y0 * keep
+        elif relu:
             Y0 = torch.relu(Y0)
         Y0.backward(dev(dY))
         want = [Y0.detach().cpu().numpy()] + [p.grad.cpu().numpy() for p in params]
