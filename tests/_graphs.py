@@ -148,6 +148,84 @@ def check_phase_graph(g: layout.HostGraph, symmetric: bool):
         assert not np.isin(g.col, np.flatnonzero(deg == 0)).any()
 
 
+LONG_N = 3000
+LONG_DEFAULT = (1023, 1024, 1025, 1536, 1537, 2047, 2048, 2049, 2600)   # threshold 1024, 512-edge chunks
+LONG_TEST = (63, 64, 65, 95, 96, 97, 128, 129)                          # threshold 64, chunks of 32 / 16
+
+
+def long_rows_graph(seed=17) -> layout.HostGraph:
+    """3 000 rows, directed and square, for the chunked hub-row paths of the edge / GAT kernels:
+    rows of exactly LONG_DEFAULT edges (either side of the default plan's threshold 1024 and of
+    its 512-edge chunk boundaries) and of exactly LONG_TEST edges (the same for the tests' plan:
+    threshold 64, chunks of 32 or 16), on even and odd rows; a block of empty rows (odd rows
+    only), one-edge rows, small random rows (1..12 edges).  Every even row has a self loop
+    (counted in its length), no odd row has one: the statistics forward takes a row's own source
+    logit from its self loop or from X[row].  Columns drawn uniformly, duplicates kept.
+    check_long_rows_graph asserts what the tests rely on."""
+    rng = np.random.default_rng(seed)
+    n = LONG_N
+    deg = rng.integers(1, 13, n)
+    deg[1001:1200:2] = 0                                 # empty rows (odd: no self loop to hold)
+    deg[1400:1500] = 1                                   # one-edge rows: a self loop / one random edge
+    for k, d in enumerate(LONG_DEFAULT + LONG_TEST):
+        deg[40 + 172 * k + k % 2] = d                    # rows 40, 213, 384, ...: even and odd
+    src = np.repeat(np.arange(n), deg)
+    dst = rng.integers(0, n, src.shape[0])
+    first = np.concatenate([[0], np.cumsum(deg)])[:-1]
+    even = np.flatnonzero((np.arange(n) % 2 == 0) & (deg > 0))
+    odd = src % 2 == 1
+    dst[odd & (dst == src)] = (src[odd & (dst == src)] + 1) % n     # no self loop on odd rows
+    dst[first[even]] = even                                          # one on every even row
+    return layout.csr_build(n, n, src.astype(np.int32), dst.astype(np.int32))
+
+
+def check_long_rows_graph(g: layout.HostGraph):
+    """What the long-row tests rely on, from the built rowptr."""
+    from gala import _abi
+    n = g.n_rows
+    deg = np.diff(g.rowptr.astype(np.int64))
+    assert n == LONG_N == g.n_cols and g.n_seg == 1 and 30_000 < g.nnz < 60_000
+    for d in LONG_DEFAULT + LONG_TEST:
+        assert (deg == d).sum() == 1, d
+    assert deg.max() == 2600 and (deg == 0).sum() >= 100 and (deg == 1).sum() >= 100
+    small = np.setdiff1d(np.arange(n), np.flatnonzero(np.isin(deg, LONG_DEFAULT + LONG_TEST)))
+    assert deg[small].max() <= 12
+    assert layout.split_threshold(n, g.nnz) == 1024
+    rows = np.repeat(np.arange(n), deg)
+    loops = np.zeros(n, bool)
+    loops[rows[rows == g.col]] = True
+    assert loops[0::2].all() and not loops[1::2].any()
+    long_ = np.flatnonzero(deg > 64)
+    assert (long_ % 2 == 0).any() and (long_ % 2 == 1).any()
+
+    def plan(threshold, chunk):
+        nr, nc = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        _abi.call("gala_host_split_plan", n, g.rowptr.ctypes.data, threshold, chunk, None, None, None,
+                  nr.ctypes.data, nc.ctypes.data)
+        return int(nr[0]), int(nc[0])
+    hub = [d for d in LONG_DEFAULT if d > 1024]
+    mid = [d for d in LONG_DEFAULT + LONG_TEST if d > 64]
+    assert len(hub) == 7 and len(mid) == 15              # strictly above the threshold
+    assert plan(1024, 512) == (7, sum(-(-d // 512) for d in hub))
+    for c in (32, 16):
+        assert plan(64, c) == (15, sum(-(-d // c) for d in mid))
+
+
+_BOUND_GRAPHS = {}
+
+
+def edge_bound_graph(name) -> layout.HostGraph:
+    """The graphs of the per-element bound tests, built once: "long" (long_rows_graph, checked),
+    "long_tiled" (by 1000 columns), "empty" (with_empty_rows) and "empty_tiled" (by 300)."""
+    if not _BOUND_GRAPHS:
+        g = long_rows_graph()
+        check_long_rows_graph(g)
+        e = with_empty_rows()
+        _BOUND_GRAPHS.update(long=g, long_tiled=layout.col_tile(g, 1000), empty=e,
+                             empty_tiled=layout.col_tile(e, 300))
+    return _BOUND_GRAPHS[name]
+
+
 def features(n, F, seed=1234, integer=False):
     rng = np.random.default_rng(seed)
     if integer:

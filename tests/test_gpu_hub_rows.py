@@ -24,8 +24,10 @@ import numpy as np
 import pytest
 import torch
 
+import _edge_ref as er
 import oracle as orc
 from gala import _abi, layout, ops
+from _edge_ref import C, assert_bounded
 from _graphs import edge_values, features, powerlaw, to_oracle
 
 pytestmark = pytest.mark.gpu
@@ -112,9 +114,15 @@ def test_edge_softmax_hub_rows(hub, mode, heads):
     s = edge_values(g.nnz, heads=heads, lo=-3, hi=3, seed=8)
     d = edge_values(g.nnz, heads=heads, lo=-1, hi=1, seed=9)
     a_ref = orc.softmax_fwd(og, s, heads=heads, mode=mode)
-    check(f"softmax_fwd_m{mode}_h{heads}", host(ops.edge_softmax(dg, dev(s), heads=heads, mode=mode)), a_ref, erows)
-    check(f"softmax_bwd_m{mode}_h{heads}", host(ops.edge_softmax_bwd(dg, dev(a_ref), dev(d), heads=heads, mode=mode)),
-          orc.softmax_bwd(og, a_ref, d, heads=heads, mode=mode), erows)
+    a = host(ops.edge_softmax(dg, dev(s), heads=heads, mode=mode))
+    check(f"softmax_fwd_m{mode}_h{heads}", a, a_ref, erows)
+    ds = host(ops.edge_softmax_bwd(dg, dev(a_ref), dev(d), heads=heads, mode=mode))
+    check(f"softmax_bwd_m{mode}_h{heads}", ds, orc.softmax_bwd(og, a_ref, d, heads=heads, mode=mode), erows)
+    # per element against float64 (tests/_edge_ref.py): c * mass, which scales with the row
+    R = er.Rows(g)
+    kw = dict(g=R, per="edge", chunk=512)
+    assert_bounded(f"bounded_softmax_fwd_m{mode}_h{heads}", a, *er.softmax_fwd(R, s, heads, mode), C["alpha"], **kw)
+    assert_bounded(f"bounded_softmax_bwd_m{mode}_h{heads}", ds, *er.softmax_bwd(R, a_ref, d, heads, mode), C["ds"], **kw)
 
 
 @pytest.mark.parametrize("mode", [_abi.GALA_SOFTMAX_REF, _abi.GALA_SOFTMAX_FIXED])
@@ -138,6 +146,15 @@ def test_gat_fused_hub_rows(hub, mode, F, heads):
     check(f"gat_daL_{tag}", host(daL), daL_ref, np.repeat(hr, heads))
     if mode == _abi.GALA_SOFTMAX_FIXED:
         check(f"gat_dz_{tag}", host(dz), dz_ref, _edge_rows(g, hr, heads))
+    # per element against float64 (the backward from the alpha it was handed, al_ref)
+    R = er.Rows(g)
+    fw = er.gat_fwd(R, aL, aR, X, heads, 0.2, mode)
+    bw = er.gat_bwd(R, aL, aR, X, dY, al_ref, heads, 0.2, mode)
+    assert_bounded(f"bounded_gat_alpha_{tag}", host(al), fw.alpha, fw.alpha, C["alpha"], g=R, per="edge", chunk=512)
+    assert_bounded(f"bounded_gat_Y_{tag}", host(Y), fw.Y, fw.Y_mass, C["Y"], g=R, per="row", chunk=512)
+    assert_bounded(f"bounded_gat_daL_{tag}", host(daL), bw.daL, bw.daL_mass, C["daL"], g=R, per="row", chunk=512)
+    if mode == _abi.GALA_SOFTMAX_FIXED:
+        assert_bounded(f"bounded_gat_dz_{tag}", host(dz), bw.dz, bw.dz_mass, C["ds"], g=R, per="edge", chunk=512)
 
 
 @pytest.mark.parametrize("heads", [1, 8])
@@ -161,6 +178,18 @@ def test_gat_stats_pair_hub_rows(hub, heads):
     check(f"stats_Y_h{heads}", host(Y), ref.Y, hr)
     check(f"stats_dX_h{heads}", host(dX), ref.dX, hr)
     check(f"stats_daL_h{heads}", host(daL).reshape(-1, heads), ref.daL, hr)
+    # per element against float64 on the kernels' own source logits
+    R = er.Rows(g)
+    aRh = host(aR).reshape(-1, heads)
+    fw = er.gat_fwd(R, aL, aRh, X, heads, 0.2, er.REF, stats=True)
+    bw = er.gat_bwd(R, aL, aRh, X, dY, fw.alpha, heads, 0.2, er.REF, dX=True)
+    kw = dict(g=R, per="row", chunk=512)
+    assert_bounded(f"bounded_stats_Y_h{heads}", host(Y), fw.Y, fw.Y_mass, C["Y"], **kw)
+    assert_bounded(f"bounded_stats_q_h{heads}", host(q), fw.q, fw.q, C["alpha"], **kw)
+    assert_bounded(f"bounded_stats_Ym_h{heads}", host(Ym), fw.Ym, fw.Ym_mass, C["Y"], **kw)
+    assert_bounded(f"bounded_stats_sma_h{heads}", host(sma), fw.sma, fw.sma, C["Y"], **kw)
+    assert_bounded(f"bounded_stats_dX_h{heads}", host(dX), bw.dX, bw.dX_mass, C["Y"], **kw)
+    assert_bounded(f"bounded_stats_daL_h{heads}", host(daL), bw.daL, bw.daL_mass, C["daL"], **kw)
 
 
 def _rows_graph(g, rows):
