@@ -1172,9 +1172,35 @@ int check_in_graph(const gala_csr_t *A, int32_t fin, int32_t heads, int32_t D) {
     if (st) return st;
     if (fin < 1 || heads < 1 || D < 1) return GALA_ERR_INVALID_ARG;
     if (fin > kInMaxFin || heads > kInMaxHeads || !(D == 4 || D == 8 || D == 16 || D == 32) || A->n_seg != 1 ||
-        A->n_rows != A->n_cols || (A->split && A->split->n_rows_split > 0))
+        A->n_rows != A->n_cols)
         return GALA_ERR_UNSUPPORTED;
+    // hub rows: the kernels' chunk contract (whole 64-index column windows); no workspace here
+    if (A->split && A->split->n_rows_split > 0) {
+        if (A->split->chunk <= 0 || A->split->chunk % 64 != 0) return GALA_ERR_UNSUPPORTED;
+        if (A->split->threshold < 1) return GALA_ERR_INVALID_ARG;
+    }
     return GALA_OK;
+}
+
+// The kernels' sum over a row's edges: `edge(e, Z)` adds edge e's terms into the nz
+// accumulators Z.  A hub row of A's plan (longer than its threshold) is summed as per-chunk
+// partials (each from zero, in CSR order) added in ascending chunk order -- the association
+// of k_gat_in_chunks and the persistent kernels' combine; every other row as one chain.
+template <typename Edge>
+void sum_row_edges(const gala_csr_t *A, int64_t r, std::vector<float> &Z, std::vector<float> &part, Edge &&edge) {
+    const int64_t e0 = A->rowptr[r], e1 = A->rowptr[r + 1];
+    std::fill(Z.begin(), Z.end(), 0.0f);
+    const gala_split_plan_t *plan = A->split;
+    if (!(plan && plan->n_rows_split > 0 && e1 - e0 > plan->threshold)) {
+        for (int64_t e = e0; e < e1; ++e) edge(e, Z.data());
+        return;
+    }
+    part.resize(Z.size());
+    for (int64_t c0 = e0; c0 < e1; c0 += plan->chunk) {
+        std::fill(part.begin(), part.end(), 0.0f);
+        for (int64_t e = c0; e < std::min<int64_t>(c0 + plan->chunk, e1); ++e) edge(e, part.data());
+        for (size_t i = 0; i < Z.size(); ++i) Z[i] = Z[i] + part[i];
+    }
 }
 
 // the d_aL dots over D / 4 lanes of four features each, summed by the kernels' xor butterfly
@@ -1272,13 +1298,12 @@ extern "C" int gala_cpu_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order
     std::vector<float> qv((size_t)A->n_rows * H);
 #pragma omp parallel
     {
-        std::vector<float> Z((size_t)16 * kInTiles * 16);   // [variant][tile][m]
+        std::vector<float> Z((size_t)16 * kInTiles * 16), part;   // [variant][tile][m]
 #pragma omp for schedule(dynamic, kRowChunk)
         for (int64_t ri = 0; ri < A->n_rows; ++ri) {
             const int64_t r = order ? order[ri] : ri;
-            std::fill(Z.begin(), Z.end(), 0.0f);
             const float *xr = Xext + r * kInLd;
-            for (int64_t e = A->rowptr[r]; e < A->rowptr[r + 1]; ++e) {
+            sum_row_edges(A, r, Z, part, [&](int64_t e, float *Z) {
                 const float *xc = Xext + (int64_t)A->col[e] * kInLd;
                 float pv[8], mp[8];
                 for (int h = 0; h < 8; ++h) {
@@ -1298,7 +1323,7 @@ extern "C" int gala_cpu_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order
                             z = fmaf(a, bv, z);
                         }
                 }
-            }
+            });
             for (int h = 0; h < H; ++h) {
                 const float S = Z[((size_t)h * kInTiles + 4) * 16 + 12];
                 const float Sm = Z[((size_t)(h + 8) * kInTiles + 4) * 16 + 12];
@@ -1362,7 +1387,7 @@ extern "C" int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *orde
     const int F = H * D;
 #pragma omp parallel
     {
-        std::vector<float> T((size_t)kInMaxHeads * kInTiles * 16);
+        std::vector<float> T((size_t)kInMaxHeads * kInTiles * 16), cpart;
 #pragma omp for schedule(dynamic, 1)
         for (int g = 0; g < grid; ++g) {
             float *Mg = part + (int64_t)g * per;
@@ -1372,9 +1397,8 @@ extern "C" int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *orde
                     const int64_t ci = blk * kInWaves + w;
                     if (ci >= n) break;
                     const int64_t c = order ? order[ci] : ci;
-                    std::fill(T.begin(), T.end(), 0.0f);
                     const float *xc = Xext + c * kInLd;
-                    for (int64_t e = AT->rowptr[c]; e < AT->rowptr[c + 1]; ++e) {
+                    sum_row_edges(AT, c, T, cpart, [&](int64_t e, float *T) {
                         const float *xr = Xext + (int64_t)AT->col[e] * kInLd;
                         for (int h = 0; h < H; ++h) {
                             const float t = xr[aL_slot(h)] + xc[aR_slot(h)];
@@ -1386,7 +1410,7 @@ extern "C" int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *orde
                                     z = fmaf(x, a, z);
                                 }
                         }
-                    }
+                    });
                     for (int h = 0; h < H; ++h) {
                         float dym[32];   // dY, masked by relu(Y) > 0 with the fused ReLU
                         const float *yh = Y + c * ldy + (int64_t)h * D;

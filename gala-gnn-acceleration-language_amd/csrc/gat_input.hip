@@ -38,6 +38,14 @@
 // backward -- and every sum is an f32 fmaf chain, regrouped (edge order inside an MFMA k-step,
 // the input-space association); the layer is checked against the oracle's pass-by-pass REF
 // layer at the Products shape (tests/test_gpu_gat_input.py).
+//
+// Hub rows (A->split with rows longer than its threshold; chunk a positive multiple of 64):
+// the pre-pass k_gat_in_chunks sums every chunk of a hub row in a wave of its own into the
+// plan's workspace, and the persistent kernels add a hub row's chunk tiles in ascending chunk
+// order instead of walking it (T mode's q likewise: per-chunk sums, combined in order) -- all
+// on the caller's stream, no atomics.  Rows at or below the threshold are summed as without a
+// plan (tests/test_gpu_gat_input_hub.py).
+#include <cstdint>
 #include <cstdlib>
 
 #include "edge_common.h"
@@ -157,6 +165,7 @@ struct InFwdParams {
     int64_t ldy;
     int32_t relu;   // GALA_GAT_IN_RELU: Y = relu(the aggregation) (the layer's NON_LNR_OP_RELU)
     float *T;       // T mode: the backward's per-column aggregates (see k_gat_in_fwd), else null
+    HubSplit hub;   // the hub-row plan (see hub_chunks); threshold INT32_MAX: no hub rows
 };
 
 // the gathered extended row of edge (4s + kq) of a 16-edge batch: column from the row's
@@ -204,27 +213,68 @@ __device__ __forceinline__ void mfma_batch(const f4v (&xa)[4], const f4v (&xb)[4
 // bounds (scalar loads), column window, row-local slot (`side`) and first batch are requested
 // while this row is walked.  The cursor holds the current row; walk() advances it to `next`
 // (-1: none).
+// The unit walked is a row (RowSeg) or one chunk of a hub row (ChunkSeg, the pre-pass
+// k_gat_in_chunks): edges [e0, end) and the row whose side values the unit takes.
 struct RowCursor {
     int64_t e0 = 0;
     int32_t deg = 0, win = 0;
+    int32_t hub = 0;       // a hub row (RowSeg): its length; deg is then 0 -- no edges to walk or prefetch
     float side = 0.0f;     // xext[row * 128 + side_slot]: aL (forward) / aR (backward) of the lane's head
     float side2 = 0.0f;    // xext[row * 128 + side_slot2] (side_slot2 >= 0): the forward's aR for T
     f4v xa[4], xb[4];      // the row's first batch (requested)
 };
 
-__device__ __forceinline__ void cursor_start(RowCursor &c, const int32_t *rowptr, const int32_t *col,
-                                             const float *xext, int64_t row, int side_slot, int side_slot2, bool side_ok,
-                                             int lane) {
+// rows of the pattern; rows longer than thr (the plan's threshold, INT32_MAX without hub rows)
+// are hub rows, whose chunks the pre-pass has summed
+struct RowSeg {
+    const int32_t *rowptr;
+    int32_t thr;
+    __device__ __forceinline__ void bounds(int64_t row, int64_t &e0, int32_t &end, int64_t &srow) const {
+        const int64_t nx = __builtin_amdgcn_readfirstlane((int32_t)row);
+        e0 = rowptr[nx];
+        end = rowptr[nx + 1];
+        srow = row;
+    }
+    __device__ __forceinline__ int32_t hub_len(int32_t deg) const { return deg > thr ? deg : 0; }
+};
+
+// chunk c of the hub-row plan: edges [k * chunk, min((k + 1) * chunk, deg)) of row rows[chunk_row[c]],
+// k = c - row_chunk0[chunk_row[c]]
+struct ChunkSeg {
+    const int32_t *rowptr;
+    HubSplit hub;
+    __device__ __forceinline__ void bounds(int64_t c, int64_t &e0, int32_t &end, int64_t &srow) const {
+        const int64_t cx = __builtin_amdgcn_readfirstlane((int32_t)c);
+        const int32_t ri = hub.chunk_row[cx];
+        const int64_t row = hub.rows[ri];
+        const int64_t r1 = rowptr[row + 1];
+        e0 = rowptr[row] + (cx - hub.row_chunk0[ri]) * (int64_t)hub.chunk;
+        if (e0 > r1) e0 = r1;
+        end = (int32_t)(e0 + hub.chunk < r1 ? e0 + hub.chunk : r1);
+        srow = row;
+    }
+    __device__ __forceinline__ int32_t hub_len(int32_t) const { return 0; }
+};
+
+template <typename Seg>
+__device__ __forceinline__ void cursor_start(RowCursor &c, const Seg &seg, const int32_t *col, const float *xext,
+                                             int64_t id, int side_slot, int side_slot2, bool side_ok, int lane) {
     const int n16 = lane & 15, kq = lane >> 4;
     c.e0 = 0;
     c.deg = 0;
+    c.hub = 0;
     c.side = 0.0f;
     c.side2 = 0.0f;
-    if (row < 0) return;
-    c.e0 = uniform(rowptr[row]);
-    c.deg = uniform(rowptr[row + 1]) - (int32_t)c.e0;
-    c.side = side_ok ? xext[row * kInLd + side_slot] : 0.0f;
-    if (side_slot2 >= 0) c.side2 = side_ok ? xext[row * kInLd + side_slot2] : 0.0f;
+    if (id < 0) return;
+    int64_t e0, srow;
+    int32_t end;
+    seg.bounds(id, e0, end, srow);
+    c.e0 = uniform((int32_t)e0);
+    c.deg = uniform(end) - (int32_t)c.e0;
+    c.hub = seg.hub_len(c.deg);
+    if (c.hub) c.deg = 0;
+    c.side = side_ok ? xext[srow * kInLd + side_slot] : 0.0f;
+    if (side_slot2 >= 0) c.side2 = side_ok ? xext[srow * kInLd + side_slot2] : 0.0f;
     if (c.deg > 0) {
         c.win = col[c.e0 + (lane < c.deg ? lane : c.deg - 1)];
         load_batch(xext, c.win, 0, kq, n16, c.xa, c.xb);
@@ -232,29 +282,26 @@ __device__ __forceinline__ void cursor_start(RowCursor &c, const int32_t *rowptr
 }
 
 // body(xa, xb, j0, deg): the MFMA work of one loaded 16-edge batch
-template <typename Body>
-__device__ __forceinline__ void cursor_walk(RowCursor &c, const int32_t *rowptr, const int32_t *col,
-                                            const float *xext, int64_t next, int side_slot, int side_slot2,
-                                            bool side_ok, int lane, Body &&body) {
+template <typename Seg, typename Body>
+__device__ __forceinline__ void cursor_walk(RowCursor &c, const Seg &seg, const int32_t *col, const float *xext,
+                                            int64_t next, int side_slot, int side_slot2, bool side_ok, int lane,
+                                            Body &&body) {
     const int n16 = lane & 15, kq = lane >> 4;
     // the next row's bounds: scalar loads (their own counter), waited for only below
-    int64_t ne0 = 0;
+    int64_t ne0 = 0, nrow = 0;
     int32_t nend = 0;
-    if (next >= 0) {
-        const int64_t nx = __builtin_amdgcn_readfirstlane((int32_t)next);
-        ne0 = rowptr[nx];
-        nend = rowptr[nx + 1];
-    }
+    if (next >= 0) seg.bounds(next, ne0, nend, nrow);
     int32_t nwin = 0;
     float nside = 0.0f, nside2 = 0.0f;
     bool next_issued = false;
     auto issue_next = [&]() {
         if (next < 0 || next_issued) return;
         next_issued = true;
-        const int32_t nd = nend - (int32_t)ne0;
+        int32_t nd = nend - (int32_t)ne0;
+        if (seg.hub_len(nd)) nd = 0;   // a hub row has no edges to prefetch
         if (nd > 0) nwin = col[ne0 + (lane < nd ? lane : nd - 1)];
-        nside = side_ok ? xext[next * kInLd + side_slot] : 0.0f;
-        if (side_slot2 >= 0) nside2 = side_ok ? xext[next * kInLd + side_slot2] : 0.0f;
+        nside = side_ok ? xext[nrow * kInLd + side_slot] : 0.0f;
+        if (side_slot2 >= 0) nside2 = side_ok ? xext[nrow * kInLd + side_slot2] : 0.0f;
     };
     for (int32_t j0 = 0; j0 < c.deg; j0 += 16) {
         const int32_t j1 = j0 + 16;
@@ -274,13 +321,81 @@ __device__ __forceinline__ void cursor_walk(RowCursor &c, const int32_t *rowptr,
             }
         }
     }
-    issue_next();   // (an empty row walked no batch)
+    issue_next();   // (an empty or hub row walked no batch)
     c.e0 = uniform((int32_t)ne0);
     c.deg = next >= 0 ? uniform(nend - (int32_t)ne0) : 0;
+    c.hub = seg.hub_len(c.deg);
+    if (c.hub) c.deg = 0;
     c.win = nwin;
     c.side = nside;
     c.side2 = nside2;
     if (c.deg > 0) load_batch(xext, c.win, 0, kq, n16, c.xa, c.xb);
+}
+
+// The B operands of the aggregation (mfma_batch's bfn), from the lane's second float4 of a
+// gathered extended row.  Forward: p of head v for variant v < 8, m * p of head v - 8 for
+// v >= 8 (al: the row's aL of the lane's head).
+struct FwdB {
+    float al, slope;
+    int H, n16;
+    __device__ __forceinline__ float operator()(const f4v &xb, bool ok) const {
+        const float t = __fadd_rn(al, xb[3]);   // lanes v < 8: aR[col][v]
+        const bool pos = t > 0.0f;
+        float pv = ref_exp(pos ? t : __fmul_rn(t, slope));
+        if (!(ok && n16 < H)) pv = 0.0f;
+        const float mp = pos ? pv : __fmul_rn(pv, slope);
+        const float mpo = ror8(mp);
+        return n16 < 8 ? pv : mpo;
+    }
+};
+
+// The backward's alpha of edge (gathered row r -> column c): p(aL[r] + aR[c]) q[r], aL[r] and
+// q[r] from r's extended row (q[h]: lane 13 + h / 3 of its edge's 16 lanes, component h % 3),
+// ar the column's aR of the lane's head
+struct AlphaB {
+    float ar, slope;
+    int H, n16, kq;
+    __device__ __forceinline__ float operator()(const f4v &xb, bool ok) const {
+        const int hq = n16 & 7;
+        const int qsrc = (16 * kq + 13 + hq / 3) * 4, qc = hq % 3;
+        const float alr = ror8(xb[3]);            // aL[r][v] from lane v + 8
+        const float q0 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[0])));
+        const float q1 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[1])));
+        const float q2 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[2])));
+        const float qr = qc == 0 ? q0 : (qc == 1 ? q1 : q2);
+        const float t = __fadd_rn(alr, ar);
+        const float pv = ref_exp(t > 0.0f ? t : __fmul_rn(t, slope));
+        const float a = __fmul_rn(pv, qr);       // K8: alpha = p * q[row]
+        return (ok && n16 < H) ? a : 0.0f;
+    }
+};
+
+// Hub rows (A->split, rows longer than the plan's threshold): no wave walks one.  The pre-pass
+// k_gat_in_chunks sums every `chunk` edges of such a row in a wave of its own and leaves the
+// accumulator tiles in the plan's workspace (kWsFwd / kWsFwdT / kWsBwd floats per chunk); the
+// persistent kernels add a hub row's partials in ascending chunk order, in the lane layout
+// they would have accumulated, and go on as for any other row.  One stream, no atomics: the
+// sums are the same run to run.
+constexpr int kWsFwd = 16 * kInTiles * 16;              // acc: 7 tiles x 64 lanes x float4
+constexpr int kWsT = kInMaxHeads * kInTiles * 16;       // accT / the backward's acc: 8 head columns (T's row layout)
+constexpr int kWsQ = kWsFwd + kWsT;                     // T mode: the q pass's 8 per-head sums of p
+constexpr int kWsFwdT = kWsQ + kInMaxHeads;
+constexpr int kWsBwd = kWsT;
+
+// first chunk and chunk count of hub row `row` (plan rows ascending); nck = 0 if the plan
+// does not hold the row
+__device__ __forceinline__ void hub_chunks(const HubSplit &hs, int64_t row, int32_t &c0, int32_t &nck) {
+    int32_t lo = 0, hi = (int32_t)hs.n_rows_split - 1;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (uniform(hs.rows[mid]) < row) lo = mid + 1;
+        else hi = mid;
+    }
+    c0 = nck = 0;
+    if (hi >= 0 && uniform(hs.rows[lo]) == row) {
+        c0 = uniform(hs.row_chunk0[lo]);
+        nck = uniform(hs.row_chunk0[lo + 1]) - c0;
+    }
 }
 
 // Forward.  Workgroup phase: wave w aggregates row order[8 blk + w] (B = p of head v for
@@ -336,16 +451,15 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_fwd(InFwdParams p) {
     };
     const bool side_ok = n16 < p.H;
     const int side2 = TM ? aR_slot(n16 & 7) : -1;
-    // T mode: q[h] of a gathered row from lane 13 + h / 3 of its edge's 16 lanes, component h % 3
-    const int hq = n16 & 7;
-    const int qsrc = (16 * kq + 13 + hq / 3) * 4, qc = hq % 3;
+    const RowSeg seg{p.rowptr, p.hub.threshold};
     RowCursor cur;
-    cursor_start(cur, p.rowptr, p.col, p.xext, row_of(blockIdx.x), aL_slot(n16 & 7), side2, side_ok, lane);
+    cursor_start(cur, seg, p.col, p.xext, row_of(blockIdx.x), aL_slot(n16 & 7), side2, side_ok, lane);
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         f4v acc[kInTiles], accT[kInTiles];
 #pragma unroll
         for (int t = 0; t < kInTiles; ++t) acc[t] = accT[t] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
         const int64_t myrow = TM ? row_of(blk) : -1;
+        const int32_t hub = cur.hub;
         // the rows this lane's projection outputs will go to (slots 2 kq, 2 kq + 1), requested
         // before the walk so the stores after the barrier wait on nothing
         int64_t prow[2];
@@ -355,35 +469,27 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_fwd(InFwdParams p) {
             prow[hs] = si < p.n_rows ? (p.order ? (int64_t)p.order[si] : si) : -1;
         }
         {
-            const float al = cur.side, ar = cur.side2;
-            const int H = p.H;
-            const float slope = p.slope;
-            auto bfn = [&](const f4v &xb, bool ok) {
-                const float t = __fadd_rn(al, xb[3]);   // lanes v < 8: aR[col][v]
-                const bool pos = t > 0.0f;
-                float pv = ref_exp(pos ? t : __fmul_rn(t, slope));
-                if (!(ok && n16 < H)) pv = 0.0f;
-                const float mp = pos ? pv : __fmul_rn(pv, slope);
-                const float mpo = ror8(mp);
-                return n16 < 8 ? pv : mpo;
-            };
+            const FwdB bfn{cur.side, p.slope, p.H, n16};
             // the backward's alpha of edge (col -> row): gala_gat_in_bwd's formula
-            auto bfnT = [&](const f4v &xb, bool ok) {
-                const float alr = ror8(xb[3]);            // aL[col][v] from lane v + 8
-                const float q0 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[0])));
-                const float q1 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[1])));
-                const float q2 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[2])));
-                const float qr = qc == 0 ? q0 : (qc == 1 ? q1 : q2);
-                const float t = __fadd_rn(alr, ar);
-                const float pv = ref_exp(t > 0.0f ? t : __fmul_rn(t, slope));
-                const float a = __fmul_rn(pv, qr);
-                return (ok && n16 < H) ? a : 0.0f;
-            };
-            cursor_walk(cur, p.rowptr, p.col, p.xext, row_of(blk + gridDim.x), aL_slot(n16 & 7), side2, side_ok, lane,
+            const AlphaB bfnT{cur.side2, p.slope, p.H, n16, kq};
+            cursor_walk(cur, seg, p.col, p.xext, row_of(blk + gridDim.x), aL_slot(n16 & 7), side2, side_ok, lane,
                         [&](const f4v (&xa)[4], const f4v (&xb)[4], int32_t j0, int32_t deg) {
                             mfma_batch(xa, xb, j0, deg, kq, n16, bfn, acc);
                             if (TM) mfma_batch(xa, xb, j0, deg, kq, n16, bfnT, accT);
                         });
+        }
+        if (hub) {   // a hub row: its chunks' tiles (k_gat_in_chunks), added in chunk order
+            int32_t c0, nck;
+            hub_chunks(p.hub, TM ? myrow : row_of(blk), c0, nck);
+            const f4v *wp = reinterpret_cast<const f4v *>(p.hub.ws + (int64_t)c0 * p.hub.ws_cols);
+            for (int32_t k = 0; k < nck; ++k, wp += p.hub.ws_cols / 4) {
+#pragma unroll
+                for (int t = 0; t < kInTiles; ++t) acc[t] += wp[t * 64 + lane];
+                if (TM && n16 < kInMaxHeads) {
+#pragma unroll
+                    for (int t = 0; t < kInTiles; ++t) accT[t] += wp[kWsFwd / 4 + (t * 4 + kq) * kInMaxHeads + n16];
+                }
+            }
         }
         if (TM && myrow >= 0 && n16 < kInMaxHeads) {
             f4v *tr = reinterpret_cast<f4v *>(p.T) + myrow * (kInTiles * 4 * kInMaxHeads);
@@ -448,6 +554,7 @@ struct InBwdParams {
     float *part;
     int32_t relu;   // Y holds relu(the aggregation): dY is masked by Y > 0 (torch's threshold_backward)    // [gridDim][H][2][kInTiles][64][4]
     const float *T; // T mode: the forward's per-column aggregates (no walk over the pattern)
+    HubSplit hub;   // the transposed pattern's hub-row plan; threshold INT32_MAX: no hub rows
 };
 
 template <int DW>   // lanes per head in the row-local d_aL dots: D / 4
@@ -480,17 +587,15 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_bwd(InBwdParams p) {
         for (int t = 0; t < kInTiles; ++t) M[mt][t] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
     const int F = p.H * p.D;
     const int64_t nblk = (p.n_rows + kInWaves - 1) / kInWaves;
-    // q[h] of a gathered row: lane 13 + h / 3 of its edge's 16 lanes, component h % 3
-    const int hq = n16 & 7;
-    const int qsrc = (16 * kq + 13 + hq / 3) * 4, qc = hq % 3;
     auto col_of = [&](int64_t b) -> int64_t {
         const int64_t ci = b * kInWaves + wave;
         if (b >= nblk || ci >= p.n_rows) return -1;
         return p.order ? (int64_t)__builtin_amdgcn_readfirstlane(p.order[ci]) : ci;
     };
     const bool side_ok = n16 < p.H;
+    const RowSeg seg{p.rowptr, p.hub.threshold};
     RowCursor cur;
-    if (!TM) cursor_start(cur, p.rowptr, p.col, p.xext, col_of(blockIdx.x), aR_slot(n16 & 7), -1, side_ok, lane);
+    if (!TM) cursor_start(cur, seg, p.col, p.xext, col_of(blockIdx.x), aR_slot(n16 & 7), -1, side_ok, lane);
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         f4v acc[kInTiles];
 #pragma unroll
@@ -516,24 +621,23 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_bwd(InBwdParams p) {
                 for (int t = 0; t < kInTiles; ++t) acc[t] = tr[(t * 4 + kq) * kInMaxHeads + n16];
             }
         } else {
-            const float ar = cur.side;
-            const int H = p.H;
-            const float slope = p.slope;
-            auto bfn = [&](const f4v &xb, bool ok) {
-                const float alr = ror8(xb[3]);            // aL[r][v] from lane v + 8
-                const float q0 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[0])));
-                const float q1 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[1])));
-                const float q2 = __int_as_float(__builtin_amdgcn_ds_bpermute(qsrc, __float_as_int(xb[2])));
-                const float qr = qc == 0 ? q0 : (qc == 1 ? q1 : q2);
-                const float t = __fadd_rn(alr, ar);
-                const float pv = ref_exp(t > 0.0f ? t : __fmul_rn(t, slope));
-                const float a = __fmul_rn(pv, qr);       // K8: alpha = p * q[row]
-                return (ok && n16 < H) ? a : 0.0f;
-            };
-            cursor_walk(cur, p.rowptr, p.col, p.xext, col_of(blk + gridDim.x), aR_slot(n16 & 7), -1, side_ok, lane,
+            const AlphaB bfn{cur.side, p.slope, p.H, n16, kq};
+            const int32_t hub = cur.hub;
+            cursor_walk(cur, seg, p.col, p.xext, col_of(blk + gridDim.x), aR_slot(n16 & 7), -1, side_ok, lane,
                         [&](const f4v (&xa)[4], const f4v (&xb)[4], int32_t j0, int32_t deg) {
                             mfma_batch(xa, xb, j0, deg, kq, n16, bfn, acc);
                         });
+            if (hub) {   // a hub column: its chunks' head columns (k_gat_in_chunks), added in chunk order
+                int32_t c0, nck;
+                hub_chunks(p.hub, c, c0, nck);
+                const f4v *wp = reinterpret_cast<const f4v *>(p.hub.ws + (int64_t)c0 * p.hub.ws_cols);
+                if (n16 < kInMaxHeads) {
+                    for (int32_t k = 0; k < nck; ++k, wp += p.hub.ws_cols / 4) {
+#pragma unroll
+                        for (int t = 0; t < kInTiles; ++t) acc[t] += wp[(t * 4 + kq) * kInMaxHeads + n16];
+                    }
+                }
+            }
         }
         if (c >= 0) {   // d_aL[c] from the forward's row statistics (gala_gat_bwd_stats_f32's formula)
             float syy = 0.0f, sym = 0.0f;
@@ -617,35 +721,123 @@ __global__ __launch_bounds__(kBlock) void k_gat_in_ar(const float *xext, int64_t
     if (i < n_rows * 8) ar[i] = xext[(i >> 3) * kInLd + aR_slot((int)(i & 7))];
 }
 
+// head h's sum of p over edges [e0, e1) in CSR order (al: the row's aL[h])
+__device__ __forceinline__ float q_edge_sum(const int32_t *col, int64_t e0, int64_t e1, float al, int h, float slope,
+                                            const float *art) {
+    float S = 0.0f;
+    // 8 edges per step, the next step's column indices requested before this step's sums
+    constexpr int U = 8;
+    int32_t cn[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) cn[k] = e0 + k < e1 ? col[e0 + k] : 0;
+    for (int64_t e = e0; e < e1; e += U) {
+        float ar[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) ar[k] = art[(int64_t)cn[k] * 8 + h];
+#pragma unroll
+        for (int k = 0; k < U; ++k) cn[k] = e + U + k < e1 ? col[e + U + k] : 0;
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            if (e + k < e1) {
+                const float t = __fadd_rn(al, ar[k]);
+                S = __fadd_rn(S, ref_exp(t > 0.0f ? t : __fmul_rn(t, slope)));
+            }
+        }
+    }
+    return S;
+}
+
+// thr: rows longer than thr are hub rows, summed by k_gat_in_q_chunks / k_gat_in_q_hub
 __global__ __launch_bounds__(kBlock) void k_gat_in_q(const int32_t *rowptr, const int32_t *col, int64_t n_rows,
-                                                     int32_t H, float slope, const float *art, float *xext) {
+                                                     int32_t H, float slope, const float *art, float *xext,
+                                                     int32_t thr) {
     const int h = threadIdx.x & 7;
     const int64_t g0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 3, gstep = ((int64_t)gridDim.x * kBlock) >> 3;
     for (int64_t r = g0; r < n_rows; r += gstep) {
         if (h >= H) continue;
         const int64_t e0 = rowptr[r], e1 = rowptr[r + 1];
+        if (e1 - e0 > thr) continue;
         const float al = xext[r * kInLd + aL_slot(h)];
-        float S = 0.0f;
-        // 8 edges per step, the next step's column indices requested before this step's sums
-        constexpr int U = 8;
-        int32_t cn[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) cn[k] = e0 + k < e1 ? col[e0 + k] : 0;
-        for (int64_t e = e0; e < e1; e += U) {
-            float ar[U];
-#pragma unroll
-            for (int k = 0; k < U; ++k) ar[k] = art[(int64_t)cn[k] * 8 + h];
-#pragma unroll
-            for (int k = 0; k < U; ++k) cn[k] = e + U + k < e1 ? col[e + U + k] : 0;
-#pragma unroll
-            for (int k = 0; k < U; ++k) {
-                if (e + k < e1) {
-                    const float t = __fadd_rn(al, ar[k]);
-                    S = __fadd_rn(S, ref_exp(t > 0.0f ? t : __fmul_rn(t, slope)));
-                }
-            }
-        }
+        const float S = q_edge_sum(col, e0, e1, al, h, slope, art);
         xext[r * kInLd + q_slot(h)] = 1.0f / __fadd_rn(S, 1e-12f);
+    }
+}
+
+// A hub row's q: 8 lanes per chunk (lane = head) sum the chunk's p in CSR order into the
+// chunk's workspace row (kWsQ + h); then one thread per (hub row, head) adds the row's
+// partial sums in chunk order.
+__global__ __launch_bounds__(kBlock) void k_gat_in_q_chunks(const int32_t *rowptr, const int32_t *col, HubSplit hub,
+                                                            int32_t H, float slope, const float *art,
+                                                            const float *xext) {
+    const int h = threadIdx.x & 7;
+    const int64_t g0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 3, gstep = ((int64_t)gridDim.x * kBlock) >> 3;
+    for (int64_t c = g0; c < hub.n_chunks; c += gstep) {
+        if (h >= H) continue;
+        const int32_t ri = hub.chunk_row[c];
+        const int64_t r = hub.rows[ri], r1 = rowptr[r + 1];
+        int64_t e0 = rowptr[r] + (c - hub.row_chunk0[ri]) * (int64_t)hub.chunk;
+        if (e0 > r1) e0 = r1;
+        const int64_t e1 = e0 + hub.chunk < r1 ? e0 + hub.chunk : r1;
+        const float al = xext[r * kInLd + aL_slot(h)];
+        hub.ws[c * hub.ws_cols + kWsQ + h] = q_edge_sum(col, e0, e1, al, h, slope, art);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_gat_in_q_hub(HubSplit hub, int32_t H, float *xext) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int h = (int)(i & 7);
+    const int64_t ri = i >> 3;
+    if (ri >= hub.n_rows_split || h >= H) return;
+    float S = 0.0f;
+    for (int64_t c = hub.row_chunk0[ri]; c < hub.row_chunk0[ri + 1]; ++c) S = __fadd_rn(S, hub.ws[c * hub.ws_cols + kWsQ + h]);
+    xext[(int64_t)hub.rows[ri] * kInLd + q_slot(h)] = 1.0f / __fadd_rn(S, 1e-12f);
+}
+
+// The hub rows' pre-pass: one wave per chunk of the plan (a persistent grid, the next chunk's
+// bounds, window and first batch requested while this one is summed), the same batches and B
+// operands as the rows' walk.  MODE 0: the forward's 16 variants (kWsFwd floats per chunk);
+// 1: T mode, those and the 8 head columns of the backward's aggregates (at kWsFwd; T's row
+// layout); 2: the backward over the transposed pattern, its 8 head columns (kWsBwd).
+struct InChunkParams {
+    const int32_t *rowptr, *col;
+    const float *xext;
+    int32_t H;
+    float slope;
+    HubSplit hub;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock, 2) void k_gat_in_chunks(InChunkParams p) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, n16 = lane & 15, kq = lane >> 4;
+    const int64_t g0 = (int64_t)blockIdx.x * (kBlock / kWave) + wave, gstep = (int64_t)gridDim.x * (kBlock / kWave);
+    const bool side_ok = n16 < p.H;
+    // the chunk's row: aL (forward) / aR (backward) of the lane's head, and the forward's aR for T
+    const int side = MODE == 2 ? aR_slot(n16 & 7) : aL_slot(n16 & 7), side2 = MODE == 1 ? aR_slot(n16 & 7) : -1;
+    const ChunkSeg seg{p.rowptr, p.hub};
+    RowCursor cur;
+    cursor_start(cur, seg, p.col, p.xext, g0 < p.hub.n_chunks ? g0 : -1, side, side2, side_ok, lane);
+    for (int64_t c = g0; c < p.hub.n_chunks; c += gstep) {
+        f4v acc[kInTiles], accT[kInTiles];
+#pragma unroll
+        for (int t = 0; t < kInTiles; ++t) acc[t] = accT[t] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+        const FwdB bf{cur.side, p.slope, p.H, n16};
+        const AlphaB ba{MODE == 2 ? cur.side : cur.side2, p.slope, p.H, n16, kq};
+        cursor_walk(cur, seg, p.col, p.xext, c + gstep < p.hub.n_chunks ? c + gstep : -1, side, side2, side_ok, lane,
+                    [&](const f4v (&xa)[4], const f4v (&xb)[4], int32_t j0, int32_t deg) {
+                        if (MODE == 2) mfma_batch(xa, xb, j0, deg, kq, n16, ba, acc);
+                        else mfma_batch(xa, xb, j0, deg, kq, n16, bf, acc);
+                        if (MODE == 1) mfma_batch(xa, xb, j0, deg, kq, n16, ba, accT);
+                    });
+        f4v *wp = reinterpret_cast<f4v *>(p.hub.ws + c * p.hub.ws_cols);
+        if (MODE != 2) {
+#pragma unroll
+            for (int t = 0; t < kInTiles; ++t) wp[t * 64 + lane] = acc[t];
+        }
+        if (MODE != 0 && n16 < kInMaxHeads) {
+            f4v *tp = wp + (MODE == 1 ? kWsFwd / 4 : 0);
+#pragma unroll
+            for (int t = 0; t < kInTiles; ++t) tp[(t * 4 + kq) * kInMaxHeads + n16] = MODE == 1 ? accT[t] : acc[t];
+        }
     }
 }
 
@@ -654,17 +846,34 @@ int grid_for(int64_t n_rows) {
     return (int)std::min<int64_t>(std::max<int64_t>(nblk, 1), kInGrid);
 }
 
-int check_in_graph(const gala_csr_t *A, int32_t fin, int32_t heads, int32_t D) {
+// need: the floats per chunk this call's pre-pass writes (gala_gat_in_split_ws_cols).  *hub:
+// the device view of A's hub-row plan, threshold INT32_MAX when A has no hub rows.
+int check_in_graph(const gala_csr_t *A, int32_t fin, int32_t heads, int32_t D, int64_t need, HubSplit *hub) {
     int st = check_csr(A);
     if (st) return st;
     if (fin < 1 || heads < 1 || D < 1) return GALA_ERR_INVALID_ARG;
     // the extended row holds at most 100 features and 8 heads; the projection's N = D <= 32
-    // with D / 4 lanes per head in the d_aL dots; one segment, a square pattern, no hub-row
-    // plan (a hub row is one wave's serial walk: those graphs stay on the statistics pair)
+    // with D / 4 lanes per head in the d_aL dots; one segment, a square pattern
     if (fin > kInMaxFin || heads > kInMaxHeads || !(D == 4 || D == 8 || D == 16 || D == 32) || A->n_seg != 1 ||
-        A->n_rows != A->n_cols || (A->split && A->split->n_rows_split > 0))
+        A->n_rows != A->n_cols)
         return GALA_ERR_UNSUPPORTED;
-    return GALA_OK;
+    *hub = HubSplit{};
+    hub->threshold = INT32_MAX;
+    const gala_split_plan_t *plan = A->split;
+    if (!plan || plan->n_rows_split <= 0) return GALA_OK;
+    // hub rows: chunks of whole 64-index column windows (and so whole 16-edge batches), and a
+    // workspace of float4 rows for the chunks' tiles
+    if (plan->chunk <= 0 || plan->chunk % 64 != 0) return GALA_ERR_UNSUPPORTED;
+    if (plan->threshold < 1 || plan->n_chunks < plan->n_rows_split || plan->n_chunks > INT32_MAX || !plan->rows ||
+        !plan->row_chunk0 || !plan->chunk_row || !plan->workspace || plan->ws_cols < need || (plan->ws_cols & 3) ||
+        ((uintptr_t)plan->workspace & 15))
+        return GALA_ERR_INVALID_ARG;
+    return hub_split(A, need, hub) ? GALA_OK : GALA_ERR_INVALID_ARG;
+}
+
+int chunk_grid(int64_t n_chunks) {
+    const int64_t blocks = (n_chunks + kBlock / kWave - 1) / (kBlock / kWave);
+    return (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), 1024);
 }
 
 }  // namespace
@@ -686,7 +895,8 @@ namespace {
 int fwd_launch(const gala_csr_t *A, const int32_t *order, int32_t fin, int32_t heads, int32_t D, float slope,
                float *Xext, const float *W, int64_t ldw, const float *b, float *Y, float *Ym, int64_t ldy, float *q,
                float *sma, int32_t flags, float *T, void *stream) {
-    int st = check_in_graph(A, fin, heads, D);
+    HubSplit hub;
+    int st = check_in_graph(A, fin, heads, D, T ? kWsFwdT : kWsFwd, &hub);
     if (st) return st;
     if (ldw < fin || ldy < (int64_t)heads * D || (flags & ~GALA_GAT_IN_RELU)) return GALA_ERR_INVALID_ARG;
     if (A->n_rows == 0) return GALA_OK;
@@ -694,8 +904,10 @@ int fwd_launch(const gala_csr_t *A, const int32_t *order, int32_t fin, int32_t h
         return GALA_ERR_INVALID_ARG;
     InFwdParams p{A->rowptr, A->col, order ? order : (A->split ? A->split->row_order : nullptr), A->n_rows, Xext, W,
                   b, ldw,
-                  fin, heads, D, slope, Y, Ym, q, sma, ldy, (flags & GALA_GAT_IN_RELU) ? 1 : 0, T};
+                  fin, heads, D, slope, Y, Ym, q, sma, ldy, (flags & GALA_GAT_IN_RELU) ? 1 : 0, T, hub};
     hipStream_t hs = (hipStream_t)stream;
+    const bool hubs = hub.threshold != INT32_MAX;
+    const InChunkParams cp{A->rowptr, A->col, Xext, heads, slope, hub};
     if (T) {
         // T's first 8 n floats hold the compact aR table until the forward writes T
         hipLaunchKernelGGL(k_gat_in_ar, dim3((unsigned)((A->n_rows * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, hs,
@@ -703,10 +915,25 @@ int fwd_launch(const gala_csr_t *A, const int32_t *order, int32_t fin, int32_t h
         if ((st = launch_status())) return st;
         const int64_t groups = (A->n_rows + kBlock / 8 - 1) / (kBlock / 8);
         hipLaunchKernelGGL(k_gat_in_q, dim3((unsigned)std::min<int64_t>(groups, 8192)), dim3(kBlock), 0, hs,
-                           A->rowptr, A->col, A->n_rows, heads, slope, T, Xext);
+                           A->rowptr, A->col, A->n_rows, heads, slope, T, Xext, hub.threshold);
         if ((st = launch_status())) return st;
+        if (hubs) {   // the hub rows' q (the pre-pass's alpha reads q of every gathered row), then their tiles
+            const int64_t cgroups = (hub.n_chunks + kBlock / 8 - 1) / (kBlock / 8);
+            hipLaunchKernelGGL(k_gat_in_q_chunks, dim3((unsigned)std::min<int64_t>(cgroups, 8192)), dim3(kBlock), 0, hs,
+                               A->rowptr, A->col, hub, heads, slope, T, Xext);
+            if ((st = launch_status())) return st;
+            hipLaunchKernelGGL(k_gat_in_q_hub, dim3((unsigned)((hub.n_rows_split * 8 + kBlock - 1) / kBlock)),
+                               dim3(kBlock), 0, hs, hub, heads, Xext);
+            if ((st = launch_status())) return st;
+            hipLaunchKernelGGL(k_gat_in_chunks<1>, dim3(chunk_grid(hub.n_chunks)), dim3(kBlock), 0, hs, cp);
+            if ((st = launch_status())) return st;
+        }
         hipLaunchKernelGGL(k_gat_in_fwd<true>, dim3(grid_for(A->n_rows)), dim3(kInBlock), 0, hs, p);
     } else {
+        if (hubs) {
+            hipLaunchKernelGGL(k_gat_in_chunks<0>, dim3(chunk_grid(hub.n_chunks)), dim3(kBlock), 0, hs, cp);
+            if ((st = launch_status())) return st;
+        }
         hipLaunchKernelGGL(k_gat_in_fwd<false>, dim3(grid_for(A->n_rows)), dim3(kInBlock), 0, hs, p);
     }
     return launch_status();
@@ -728,6 +955,15 @@ extern "C" int gala_gat_in_fwd_t_f32(const gala_csr_t *A, const int32_t *order, 
     return fwd_launch(A, order, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags, T, stream);
 }
 
+extern "C" int64_t gala_gat_in_split_ws_cols(int32_t mode) {
+    switch (mode) {
+    case GALA_GAT_IN_WS_FWD: return kWsFwd;
+    case GALA_GAT_IN_WS_FWD_T: return kWsFwdT;
+    case GALA_GAT_IN_WS_BWD: return kWsBwd;
+    default: return -1;
+    }
+}
+
 extern "C" int64_t gala_gat_in_bwd_workspace(int32_t heads) {
     if (heads < 1 || heads > kInMaxHeads) return -1;
     return (int64_t)kInGrid * heads * 2 * kInTiles * 64 * 4 * (int64_t)sizeof(float);
@@ -741,8 +977,10 @@ int bwd_launch(const gala_csr_t *AT, int64_t n_rows, const int32_t *order, int32
                void *stream) {
     float *ws = (float *)ws_;
     int st;
+    HubSplit hub{};
+    hub.threshold = INT32_MAX;
     if (AT) {
-        if ((st = check_in_graph(AT, fin, heads, D))) return st;
+        if ((st = check_in_graph(AT, fin, heads, D, kWsBwd, &hub))) return st;
         n_rows = AT->n_rows;
     } else {
         if (n_rows < 0 || fin < 1 || heads < 1 || D < 1) return GALA_ERR_INVALID_ARG;
@@ -763,8 +1001,13 @@ int bwd_launch(const gala_csr_t *AT, int64_t n_rows, const int32_t *order, int32
     const int grid = grid_for(n_rows);
     const int32_t *ord = order ? order : (AT && AT->split ? AT->split->row_order : nullptr);
     InBwdParams p{AT ? AT->rowptr : nullptr, AT ? AT->col : nullptr, ord, n_rows, Xext, dY, Y, Ym,
-                  sma, ldy, fin, heads, D, slope, daL, ws, (flags & GALA_GAT_IN_RELU) ? 1 : 0, T};
+                  sma, ldy, fin, heads, D, slope, daL, ws, (flags & GALA_GAT_IN_RELU) ? 1 : 0, T, hub};
     if (hipMemsetAsync(M, 0, outn * sizeof(float), hs) != hipSuccess) return GALA_ERR_HIP;
+    if (hub.threshold != INT32_MAX) {   // the hub columns' chunks
+        const InChunkParams cp{AT->rowptr, AT->col, Xext, heads, slope, hub};
+        hipLaunchKernelGGL(k_gat_in_chunks<2>, dim3(chunk_grid(hub.n_chunks)), dim3(kBlock), 0, hs, cp);
+        if ((st = launch_status())) return st;
+    }
 #define GALA_IN_BWD(DW)                                                                           \
     do {                                                                                          \
         if (AT) hipLaunchKernelGGL((k_gat_in_bwd<DW, false>), dim3(grid), dim3(kInBlock), 0, hs, p); \

@@ -155,6 +155,7 @@ SIGNATURES = {
     "gala_gat_in_fwd_f32": (ctypes.c_int, [_CSR, _P, _I32, _I32, _I32, _F, _P, _P, _I64, _P, _P, _P, _I64, _P, _P,
                                            _I32, _P]),
     "gala_gat_in_bwd_workspace": (ctypes.c_int64, [_I32]),
+    "gala_gat_in_split_ws_cols": (ctypes.c_int64, [_I32]),
     "gala_gat_in_bwd_f32": (ctypes.c_int, [_CSR, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P, _I64, _P, _P, _P, _P,
                                            _I64, _I32, _P]),
     "gala_gat_in_fwd_t_f32": (ctypes.c_int, [_CSR, _P, _I32, _I32, _I32, _F, _P, _P, _I64, _P, _P, _P, _I64, _P,
@@ -179,6 +180,7 @@ _lib = None
 
 
 GALA_GAT_IN_RELU = 1
+GALA_GAT_IN_WS_FWD, GALA_GAT_IN_WS_FWD_T, GALA_GAT_IN_WS_BWD = 0, 1, 2  # gala_gat_in_split_ws_cols modes
 ABI_VERSION = 6  # GALA_ABI_VERSION of include/gala_hip.h these bindings mirror
 
 

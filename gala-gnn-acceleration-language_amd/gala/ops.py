@@ -572,6 +572,11 @@ def gat_in_prep(X, u, c, heads, xext=None):
     return xext
 
 
+def _gat_in_ws_cols(g: DeviceGraph, mode: int) -> int:
+    """Floats per chunk the hub rows' pre-pass of a gala_gat_in_* call needs in g's plan (0: no hub rows)."""
+    return int(_abi.lib().gala_gat_in_split_ws_cols(mode)) if g.split_rows > 0 else 0
+
+
 def gat_in_fwd(g: DeviceGraph, xext, W, b, heads, fin, slope=0.2, order=None, relu=False, T=None, Y=None, Ym=None):
     """gala_gat_in_fwd_f32: (Y, Ym, q, sma); writes q into xext.  order: int32 row order.
     T ([N, 896], symmetric g only): gala_gat_in_fwd_t_f32, which also forms the backward's
@@ -592,11 +597,12 @@ def gat_in_fwd(g: DeviceGraph, xext, W, b, heads, fin, slope=0.2, order=None, re
     q = torch.empty(g.n_rows, heads, device=W.device, dtype=torch.float32)
     sma = torch.empty_like(q)
     flags = _abi.GALA_GAT_IN_RELU if relu else 0
+    csr = g.csr(_gat_in_ws_cols(g, _abi.GALA_GAT_IN_WS_FWD if T is None else _abi.GALA_GAT_IN_WS_FWD_T))
     if T is None:
-        _abi.call("gala_gat_in_fwd_f32", g.csr(0), _dp(order), fin, heads, D, slope, _dp(xext), _dp(W), W.stride(0),
+        _abi.call("gala_gat_in_fwd_f32", csr, _dp(order), fin, heads, D, slope, _dp(xext), _dp(W), W.stride(0),
                   _dp(b), _dp(Y), _dp(Ym), ldy, _dp(q), _dp(sma), flags, _stream())
     else:
-        _abi.call("gala_gat_in_fwd_t_f32", g.csr(0), _dp(order), fin, heads, D, slope, _dp(xext), _dp(W),
+        _abi.call("gala_gat_in_fwd_t_f32", csr, _dp(order), fin, heads, D, slope, _dp(xext), _dp(W),
                   W.stride(0), _dp(b), _dp(Y), _dp(Ym), ldy, _dp(q), _dp(sma), flags, _dp(T), _stream())
     return Y, Ym, q, sma
 
@@ -617,7 +623,8 @@ def gat_in_bwd(gT: DeviceGraph, xext, dY, Y, Ym, sma, heads, fin, slope=0.2, ord
     ws = torch.empty(max(wsb // 4, 1), device=dY.device, dtype=torch.float32)
     flags = _abi.GALA_GAT_IN_RELU if relu else 0
     if T is None:
-        _abi.call("gala_gat_in_bwd_f32", gT.csr(0), _dp(order), fin, heads, D, slope, _dp(xext), _dp(dY), _dp(Y),
+        csr = gT.csr(_gat_in_ws_cols(gT, _abi.GALA_GAT_IN_WS_BWD))
+        _abi.call("gala_gat_in_bwd_f32", csr, _dp(order), fin, heads, D, slope, _dp(xext), _dp(dY), _dp(Y),
                   _dp(Ym), ldy, _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
     else:
         _abi.call("gala_gat_in_bwd_t_f32", n, _dp(order), fin, heads, D, _dp(T), _dp(dY), _dp(Y), _dp(Ym), ldy,

@@ -1533,6 +1533,8 @@ struct GatInputLayer : public torch::autograd::Function<GatInputLayer> {
         const bool tmode = grad && B.gat_in_fwd_t && pt.symmetric && gat_in_tmode_enabled() &&
                            N * 896 * (int64_t)sizeof(float) <= gat_in_tmode_max_bytes();
         torch::Tensor T = tmode ? torch::empty({N, 896}, fopts(x)) : torch::empty({0}, fopts(x));
+        // hub rows: the pre-pass's chunk tiles live in the plan's workspace
+        with_workspace(cv, s.off, gala_gat_in_split_ws_cols(tmode ? GALA_GAT_IN_WS_FWD_T : GALA_GAT_IN_WS_FWD));
         if (tmode)
             check(B.gat_in_fwd_t(&cv.c, pt.order.data_ptr<int32_t>(), (int32_t)fin, (int32_t)H, (int32_t)D, (float)slope,
                                  xext.data_ptr<float>(), w.data_ptr<float>(), fin, has_b ? bc.data_ptr<float>() : nullptr,
@@ -1571,6 +1573,15 @@ struct GatInputLayer : public torch::autograd::Function<GatInputLayer> {
         // regrouped by column it walks A's transposed pattern (A's own tensors when symmetric)
         const PatternT &pt = transposed_pattern(2 * li);
         CsrView cv = view(pt.rowptr, pt.col, nullptr, torch::Tensor(), 1);
+        if (T.numel() == 0) {   // the walk: the transposed pattern's hub-row plan with its workspace
+            const int64_t cols = gala_gat_in_split_ws_cols(GALA_GAT_IN_WS_BWD);
+            if (pt.split) {     // (a non-symmetric pattern's transpose is in no slot)
+                if (pt.split->plan.n_rows_split > 0) pt.split->ensure_workspace(cols);
+                cv.c.split = &pt.split->plan;
+            } else {
+                with_workspace(cv, pt.rowptr, cols);
+            }
+        }
         const Backend &B = be(x);
         auto daL = torch::empty({N, H}, fopts(x));
         auto M = torch::empty({H, D, fin + 1}, fopts(x));
@@ -1643,6 +1654,8 @@ const PatternT &transposed_pattern(int64_t idx) {
         auto ot = torch::empty({n}, io);
         check(gala_host_row_order(n, tr.data_ptr<int32_t>(), ot.data_ptr<int32_t>()), "gala_host_row_order");
         p->order_t = ot.to(dev);
+        // the transposed rowptr is in no slot: its hub-row plan is kept here
+        if (dev.is_cuda()) p->split = make_split_plan(p->rowptr, 1);
     }
     pt = p;
     return *pt;
@@ -1739,14 +1752,11 @@ bool gat_input_layer_eligible(const torch::Tensor &X, const torch::Tensor &W, in
     // the byte saving is the point: the input row narrower than the Linear's output
     if (fin >= F) return false;
     // REF on the undirected graph (slot 2li+1 = slot 2li, the reference's A-not-A^T backward
-    // then equals the transposed regrouping), one segment, no hub-row plan
+    // then equals the transposed regrouping), one segment; hub rows run as chunk partials
+    // (make_split_plan's 512-edge chunks meet the kernels' multiple-of-64 contract)
     Slot s = slot(2 * li);
     if (!recompute_attention(li, mode) || s.segs != 1 || s.weighted || global_slots().nsamples > 0) return false;
     if (s.off.device() != X.device()) return false;
-    if (s.off.is_cuda()) {
-        SplitState *sp = find_split(s.off);
-        if (sp && sp->plan.n_rows_split > 0) return false;
-    }
     return true;
 }
 

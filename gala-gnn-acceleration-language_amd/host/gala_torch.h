@@ -66,6 +66,7 @@ struct PatternT {
     torch::Tensor rowptr, col;
     bool symmetric = false;
     torch::Tensor order, order_t;   // rows of the pattern / of its transpose by descending degree
+    std::shared_ptr<SplitState> split;   // a non-symmetric pattern's transpose: its hub-row plan (GPU; else null)
 };
 
 // The generated program's graph slots (codegen/gala.cu:32-43): slot 2*li is layer li's

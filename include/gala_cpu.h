@@ -139,6 +139,9 @@ int gala_cpu_dense_grad_f32(int64_t n_rows, int32_t K, int32_t M, const float *X
                             const float *dY, int64_t ldy, float *dW, float *db,
                             int32_t accumulate, void *workspace, int64_t workspace_bytes,
                             void *stream);
+/* The input-space GAT layer.  A plan with hub rows (A->split / AT->split, chunk a positive
+ * multiple of 64 as on the GPU) needs no workspace or index arrays here: a hub row is summed
+ * as per-chunk partials added in chunk order, the GPU kernels' association. */
 int gala_cpu_gat_in_prep_f32(int64_t n, int32_t fin, const float *Xin, int64_t ldxin, int32_t heads,
                              const float *u, const float *c, float *Xext, void *stream);
 int gala_cpu_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order, int32_t fin, int32_t heads, int32_t D, float slope,

@@ -579,10 +579,25 @@ int gala_head_attn_bwd_f32(int64_t n_rows, int32_t F, int32_t heads, const float
  *     gradient of relu(Y), masked by relu(Y) > 0 (torch's threshold_backward); the d_aL dots
  *     <dY, Y> are then the same sums over relu(Y).
  * Limits (else GALA_ERR_UNSUPPORTED, callers keep the statistics pair): fin <= 100, heads
- * <= 8, D in {4, 8, 16, 32}, one segment, a square pattern, no hub rows in A->split (a hub
- * row would be one wave's serial walk).  Sums are regrouped (the matrix cores sum four edges
- * per step; the input-space association): fp32 rounding of the reference, checked at 1e-4.
+ * <= 8, D in {4, 8, 16, 32}, one segment, a square pattern, and, when A->split (AT->split) has
+ * hub rows, a chunk size that is a positive multiple of 64.  Sums are regrouped (the matrix
+ * cores sum four edges per step; the input-space association): fp32 rounding of the
+ * reference, checked at 1e-4.
+ * Hub rows (A->split->n_rows_split > 0): a pre-pass on the caller's stream sums each chunk of
+ * a hub row in a wave of its own into A->split->workspace, and the row's wave adds those
+ * partials in ascending chunk order instead of walking the row -- no side stream, no atomics,
+ * bit-identical run to run; T mode's q of a hub row is likewise the sum of per-chunk sums.
+ * The plan must carry a 16-B aligned workspace with ws_cols a multiple of 4 and at least
+ * gala_gat_in_split_ws_cols(mode) for the call (else GALA_ERR_INVALID_ARG, nothing launched):
+ *   GALA_GAT_IN_WS_FWD   gala_gat_in_fwd_f32    (1792 floats per chunk)
+ *   GALA_GAT_IN_WS_FWD_T gala_gat_in_fwd_t_f32  (2696)
+ *   GALA_GAT_IN_WS_BWD   gala_gat_in_bwd_f32, for AT's plan (896)
+ * -1 for any other mode.  Rows at or below the threshold are summed exactly as without a plan.
  */
+#define GALA_GAT_IN_WS_FWD 0
+#define GALA_GAT_IN_WS_FWD_T 1
+#define GALA_GAT_IN_WS_BWD 2
+int64_t gala_gat_in_split_ws_cols(int32_t mode);
 int gala_gat_in_prep_f32(int64_t n, int32_t fin, const float *Xin, int64_t ldxin, int32_t heads,
                          const float *u, const float *c, float *Xext, void *stream);
 #define GALA_GAT_IN_RELU 1   /* the layer's ReLU fused: Y = relu(.) forward, dY masked by Y > 0 backward */

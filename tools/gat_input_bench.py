@@ -4,7 +4,11 @@ replaces (ffn_apply -> head_attn_apply -> gat_aggregate_ffn_apply: the Linear ou
 gathered, the row-statistics GAT pair), forward and backward with autograd, alternated in one
 process.  Prints one JSON line per variant.
 
-    python tools/gat_input_bench.py [--scale 1.0] [--reps 5]
+    python tools/gat_input_bench.py [--graph uniform|rmat] [--scale 1.0] [--reps 5]
+
+--graph rmat: the Products-shaped R-MAT graph, whose split plan has hub rows (the input-space
+kernels sum them as chunk partials; `chain` is what ran on such graphs before they did).  The
+last line then also gives the plan's hub rows, chunks and the chunk workspace in bytes.
 """
 import argparse
 import json
@@ -21,13 +25,14 @@ sys.path.insert(0, os.path.join(ROOT, "gala-gnn-acceleration-language_amd"))
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--graph", choices=("uniform", "rmat"), default="uniform")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
     import bench
     import gala
     E = gala.torch_ext()
-    g = bench.products_graph("uniform", a.scale)
+    g = bench.products_graph(a.graph, a.scale)
     E.slots_clear()
     off, cols = torch.from_numpy(g.rowptr).cuda(), torch.from_numpy(g.col).cuda()
     vals = torch.ones(g.nnz, device="cuda")
@@ -81,11 +86,23 @@ def main():
     E_ = g.nnz
     for name in variants:
         f, bw = float(np.median(res[name]["fwd"])), float(np.median(res[name]["bwd"]))
-        print(json.dumps({"variant": name, "n": g.n_rows, "nnz": E_, "fin": fin, "heads": H, "D": D,
+        print(json.dumps({"variant": name, "graph": a.graph, "n": g.n_rows, "nnz": E_, "fin": fin, "heads": H, "D": D,
                           "fwd_ms": round(f, 3), "bwd_ms": round(bw, 3), "layer_ms": round(f + bw, 3),
                           "edges_per_s": E_ / ((f + bw) / 1e3), "fwd_all": res[name]["fwd"],
                           "bwd_all": res[name]["bwd"]}), flush=True)
-    print(json.dumps({"max_rel_diff_vs_chain": err}), flush=True)
+    # the mirror's plan for this graph (make_split_plan: the default threshold, 512-edge chunks)
+    import ctypes
+    from gala import _abi, layout
+    thr = layout.split_threshold(g.n_rows, g.nnz)
+    nr, nc = ctypes.c_int64(0), ctypes.c_int64(0)
+    _abi.call("gala_host_split_plan", g.n_rows, g.rowptr.ctypes.data, thr, 512, None, None, None, ctypes.byref(nr),
+              ctypes.byref(nc))
+    deg = np.diff(g.rowptr)
+    cols = {m: int(_abi.lib().gala_gat_in_split_ws_cols(i)) for i, m in enumerate(("fwd", "fwd_t", "bwd"))}
+    print(json.dumps({"max_rel_diff_vs_chain": err, "graph": a.graph, "threshold": int(thr), "hub_rows": nr.value,
+                      "n_chunks": nc.value, "hub_edge_share": float(deg[deg > thr].sum() / max(g.nnz, 1)),
+                      "longest_row": int(deg.max()), "ws_cols": cols,
+                      "ws_bytes": {m: nc.value * c * 4 for m, c in cols.items()}}), flush=True)
 
 
 if __name__ == "__main__":
