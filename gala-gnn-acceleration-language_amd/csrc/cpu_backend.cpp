@@ -1167,13 +1167,18 @@ inline int tile_feature(int t, int m, int fin) {
 // extended-row slot of tile t's row m (the kernels' lane / component layout)
 inline int tile_slot(int t, int m) { return t < 4 ? 4 * m + t : 64 + 4 * m + (t - 4); }
 
-int check_in_graph(const gala_csr_t *A, int32_t fin, int32_t heads, int32_t D) {
+// row_base: the table row of A's row 0; kSquare: the square entry points (row_base 0, a square pattern only)
+constexpr int64_t kSquare = INT64_MIN;
+int check_in_graph(const gala_csr_t *A, int64_t &row_base, int32_t fin, int32_t heads, int32_t D) {
     int st = check_csr(A);
     if (st) return st;
-    if (fin < 1 || heads < 1 || D < 1) return GALA_ERR_INVALID_ARG;
+    const bool square = row_base == kSquare;
+    if (square) row_base = 0;
+    if (fin < 1 || heads < 1 || D < 1 || row_base < 0) return GALA_ERR_INVALID_ARG;
     if (fin > kInMaxFin || heads > kInMaxHeads || !(D == 4 || D == 8 || D == 16 || D == 32) || A->n_seg != 1 ||
-        A->n_rows != A->n_cols)
+        A->n_rows > A->n_cols || (square && A->n_rows != A->n_cols))
         return GALA_ERR_UNSUPPORTED;
+    if (row_base + A->n_rows > A->n_cols) return GALA_ERR_INVALID_ARG;
     // hub rows: the kernels' chunk contract (whole 64-index column windows); no workspace here
     if (A->split && A->split->n_rows_split > 0) {
         if (A->split->chunk <= 0 || A->split->chunk % 64 != 0) return GALA_ERR_UNSUPPORTED;
@@ -1282,12 +1287,11 @@ extern "C" int gala_cpu_gat_in_prep_f32(int64_t n, int32_t fin, const float *Xin
     return GALA_OK;
 }
 
-extern "C" int gala_cpu_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order_in, int32_t fin, int32_t heads,
-                                       int32_t D, float slope,
-                                       float *Xext, const float *W, int64_t ldw, const float *b, float *Y,
-                                       float *Ym, int64_t ldy, float *q, float *sma, int32_t flags, void *stream) {
-    (void)stream;
-    int st = check_in_graph(A, fin, heads, D);
+namespace {
+int gat_in_fwd_host(const gala_csr_t *A, int64_t row_base, const int32_t *order_in, int32_t fin, int32_t heads,
+                    int32_t D, float slope, float *Xext, const float *W, int64_t ldw, const float *b, float *Y,
+                    float *Ym, int64_t ldy, float *q, float *sma, int32_t flags) {
+    int st = check_in_graph(A, row_base, fin, heads, D);
     if (st) return st;
     if (ldw < fin || ldy < (int64_t)heads * D || (flags & ~GALA_GAT_IN_RELU)) return GALA_ERR_INVALID_ARG;
     if (A->n_rows == 0) return GALA_OK;
@@ -1302,7 +1306,7 @@ extern "C" int gala_cpu_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order
 #pragma omp for schedule(dynamic, kRowChunk)
         for (int64_t ri = 0; ri < A->n_rows; ++ri) {
             const int64_t r = order ? order[ri] : ri;
-            const float *xr = Xext + r * kInLd;
+            const float *xr = Xext + (row_base + r) * kInLd;
             sum_row_edges(A, r, Z, part, [&](int64_t e, float *Z) {
                 const float *xc = Xext + (int64_t)A->col[e] * kInLd;
                 float pv[8], mp[8];
@@ -1353,7 +1357,56 @@ extern "C" int gala_cpu_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order
     // slots, which no aggregation reads)
 #pragma omp parallel for schedule(static)
     for (int64_t r = 0; r < A->n_rows; ++r)
-        for (int h = 0; h < H; ++h) Xext[r * kInLd + q_slot(h)] = qv[(size_t)r * H + h];
+        for (int h = 0; h < H; ++h) Xext[(row_base + r) * kInLd + q_slot(h)] = qv[(size_t)r * H + h];
+    return GALA_OK;
+}
+}  // namespace
+
+extern "C" int gala_cpu_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order_in, int32_t fin, int32_t heads,
+                                       int32_t D, float slope,
+                                       float *Xext, const float *W, int64_t ldw, const float *b, float *Y,
+                                       float *Ym, int64_t ldy, float *q, float *sma, int32_t flags, void *stream) {
+    (void)stream;
+    return gat_in_fwd_host(A, kSquare, order_in, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags);
+}
+
+extern "C" int gala_cpu_gat_in_fwd_rect_f32(const gala_csr_t *A, int64_t row_base, const int32_t *order_in,
+                                            int32_t fin, int32_t heads, int32_t D, float slope, float *Xext,
+                                            const float *W, int64_t ldw, const float *b, float *Y, float *Ym,
+                                            int64_t ldy, float *q, float *sma, int32_t flags, void *stream) {
+    (void)stream;
+    if (row_base == kSquare) return GALA_ERR_INVALID_ARG;
+    return gat_in_fwd_host(A, row_base, order_in, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags);
+}
+
+extern "C" int gala_cpu_gat_in_q_gather_f32(int64_t n_idx, const int32_t *rows, int64_t n_table, int32_t heads,
+                                            const float *Xext, float *dst, void *stream) {
+    (void)stream;
+    if (n_idx < 0 || n_table < 0 || heads < 1) return GALA_ERR_INVALID_ARG;
+    if (heads > kInMaxHeads) return GALA_ERR_UNSUPPORTED;
+    if (n_idx == 0) return GALA_OK;
+    if (!rows || !Xext || !dst) return GALA_ERR_INVALID_ARG;
+    for (int64_t k = 0; k < n_idx; ++k)
+        for (int h = 0; h < heads; ++h) {
+            const int64_t r = rows[k];
+            dst[k * heads + h] = (r >= 0 && r < n_table) ? Xext[r * kInLd + q_slot(h)] : 0.0f;
+        }
+    return GALA_OK;
+}
+
+extern "C" int gala_cpu_gat_in_q_scatter_f32(int64_t n, const int32_t *rows, int64_t row0, int64_t n_table,
+                                             int32_t heads, const float *src, float *Xext, void *stream) {
+    (void)stream;
+    if (n < 0 || n_table < 0 || heads < 1) return GALA_ERR_INVALID_ARG;
+    if (!rows && (row0 < 0 || row0 + n > n_table)) return GALA_ERR_INVALID_ARG;
+    if (heads > kInMaxHeads) return GALA_ERR_UNSUPPORTED;
+    if (n == 0) return GALA_OK;
+    if (!src || !Xext) return GALA_ERR_INVALID_ARG;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t r = rows ? (int64_t)rows[k] : row0 + k;
+        if (r < 0 || r >= n_table) continue;
+        for (int h = 0; h < heads; ++h) Xext[r * kInLd + q_slot(h)] = src[k * heads + h];
+    }
     return GALA_OK;
 }
 
@@ -1362,13 +1415,11 @@ extern "C" int64_t gala_cpu_gat_in_bwd_workspace(int32_t heads) {
     return (int64_t)kInGrid * heads * 2 * kInTiles * 64 * 4 * (int64_t)sizeof(float);
 }
 
-extern "C" int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *order_in, int32_t fin, int32_t heads,
-                                       int32_t D, float slope,
-                                       const float *Xext, const float *dY, const float *Y, const float *Ym,
-                                       int64_t ldy, const float *sma, float *daL, float *M, void *ws,
-                                       int64_t ws_bytes, int32_t flags, void *stream) {
-    (void)stream;
-    int st = check_in_graph(AT, fin, heads, D);
+namespace {
+int gat_in_bwd_host(const gala_csr_t *AT, int64_t row_base, const int32_t *order_in, int32_t fin, int32_t heads,
+                    int32_t D, float slope, const float *Xext, const float *dY, const float *Y, const float *Ym,
+                    int64_t ldy, const float *sma, float *daL, float *M, void *ws, int64_t ws_bytes, int32_t flags) {
+    int st = check_in_graph(AT, row_base, fin, heads, D);
     if (st) return st;
     if (ldy < (int64_t)heads * D || (ldy & 3) || (flags & ~GALA_GAT_IN_RELU)) return GALA_ERR_INVALID_ARG;
     if (!M) return GALA_ERR_INVALID_ARG;
@@ -1397,7 +1448,7 @@ extern "C" int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *orde
                     const int64_t ci = blk * kInWaves + w;
                     if (ci >= n) break;
                     const int64_t c = order ? order[ci] : ci;
-                    const float *xc = Xext + c * kInLd;
+                    const float *xc = Xext + (row_base + c) * kInLd;
                     sum_row_edges(AT, c, T, cpart, [&](int64_t e, float *T) {
                         const float *xr = Xext + (int64_t)AT->col[e] * kInLd;
                         for (int h = 0; h < H; ++h) {
@@ -1440,4 +1491,26 @@ extern "C" int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *orde
         M[i] = s;
     }
     return GALA_OK;
+}
+}  // namespace
+
+extern "C" int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *order_in, int32_t fin, int32_t heads,
+                                       int32_t D, float slope,
+                                       const float *Xext, const float *dY, const float *Y, const float *Ym,
+                                       int64_t ldy, const float *sma, float *daL, float *M, void *ws,
+                                       int64_t ws_bytes, int32_t flags, void *stream) {
+    (void)stream;
+    return gat_in_bwd_host(AT, kSquare, order_in, fin, heads, D, slope, Xext, dY, Y, Ym, ldy, sma, daL, M, ws,
+                           ws_bytes, flags);
+}
+
+extern "C" int gala_cpu_gat_in_bwd_rect_f32(const gala_csr_t *AT, int64_t row_base, const int32_t *order_in,
+                                            int32_t fin, int32_t heads, int32_t D, float slope, const float *Xext,
+                                            const float *dY, const float *Y, const float *Ym, int64_t ldy,
+                                            const float *sma, float *daL, float *M, void *ws, int64_t ws_bytes,
+                                            int32_t flags, void *stream) {
+    (void)stream;
+    if (row_base == kSquare) return GALA_ERR_INVALID_ARG;
+    return gat_in_bwd_host(AT, row_base, order_in, fin, heads, D, slope, Xext, dY, Y, Ym, ldy, sma, daL, M, ws,
+                           ws_bytes, flags);
 }

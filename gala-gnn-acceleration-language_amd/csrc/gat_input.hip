@@ -45,6 +45,13 @@
 // order instead of walking it (T mode's q likewise: per-chunk sums, combined in order) -- all
 // on the caller's stream, no atomics.  Rows at or below the threshold are summed as without a
 // plan (tests/test_gpu_gat_input_hub.py).
+//
+// Rectangular patterns (the *_rect_* entry points: a rank of a row partition, whose columns
+// index a table [lower halo | own rows | higher halo]): n_rows <= n_cols, and row r's own
+// extended row is table row row_base + r.  The gathers index the table (xext) by column; every
+// access to a row's own extended row -- the side slots, q, the q pass, the chunk pre-pass --
+// goes through xown = xext + row_base * 128.  The square entry points are row_base 0 on a
+// square pattern (tests/test_gpu_gat_input_rect.py).
 #include <cstdint>
 #include <cstdlib>
 
@@ -156,7 +163,8 @@ __global__ __launch_bounds__(kBlock) void k_gat_in_prep(InPrepParams p) {
 struct InFwdParams {
     const int32_t *rowptr, *col, *order;
     int64_t n_rows;
-    float *xext;
+    float *xext;   // the table the columns index
+    float *xown;   // the table row of row 0 (xext + row_base * 128): every access to a row's own extended row
     const float *W, *b;
     int64_t ldw;
     int32_t fin, H, D;
@@ -219,8 +227,8 @@ struct RowCursor {
     int64_t e0 = 0;
     int32_t deg = 0, win = 0;
     int32_t hub = 0;       // a hub row (RowSeg): its length; deg is then 0 -- no edges to walk or prefetch
-    float side = 0.0f;     // xext[row * 128 + side_slot]: aL (forward) / aR (backward) of the lane's head
-    float side2 = 0.0f;    // xext[row * 128 + side_slot2] (side_slot2 >= 0): the forward's aR for T
+    float side = 0.0f;     // xown[row * 128 + side_slot]: aL (forward) / aR (backward) of the lane's head
+    float side2 = 0.0f;    // xown[row * 128 + side_slot2] (side_slot2 >= 0): the forward's aR for T
     f4v xa[4], xb[4];      // the row's first batch (requested)
 };
 
@@ -258,7 +266,7 @@ struct ChunkSeg {
 
 template <typename Seg>
 __device__ __forceinline__ void cursor_start(RowCursor &c, const Seg &seg, const int32_t *col, const float *xext,
-                                             int64_t id, int side_slot, int side_slot2, bool side_ok, int lane) {
+                                             const float *xown, int64_t id, int side_slot, int side_slot2, bool side_ok, int lane) {
     const int n16 = lane & 15, kq = lane >> 4;
     c.e0 = 0;
     c.deg = 0;
@@ -273,8 +281,8 @@ __device__ __forceinline__ void cursor_start(RowCursor &c, const Seg &seg, const
     c.deg = uniform(end) - (int32_t)c.e0;
     c.hub = seg.hub_len(c.deg);
     if (c.hub) c.deg = 0;
-    c.side = side_ok ? xext[srow * kInLd + side_slot] : 0.0f;
-    if (side_slot2 >= 0) c.side2 = side_ok ? xext[srow * kInLd + side_slot2] : 0.0f;
+    c.side = side_ok ? xown[srow * kInLd + side_slot] : 0.0f;
+    if (side_slot2 >= 0) c.side2 = side_ok ? xown[srow * kInLd + side_slot2] : 0.0f;
     if (c.deg > 0) {
         c.win = col[c.e0 + (lane < c.deg ? lane : c.deg - 1)];
         load_batch(xext, c.win, 0, kq, n16, c.xa, c.xb);
@@ -284,7 +292,7 @@ __device__ __forceinline__ void cursor_start(RowCursor &c, const Seg &seg, const
 // body(xa, xb, j0, deg): the MFMA work of one loaded 16-edge batch
 template <typename Seg, typename Body>
 __device__ __forceinline__ void cursor_walk(RowCursor &c, const Seg &seg, const int32_t *col, const float *xext,
-                                            int64_t next, int side_slot, int side_slot2, bool side_ok, int lane,
+                                            const float *xown, int64_t next, int side_slot, int side_slot2, bool side_ok, int lane,
                                             Body &&body) {
     const int n16 = lane & 15, kq = lane >> 4;
     // the next row's bounds: scalar loads (their own counter), waited for only below
@@ -300,8 +308,8 @@ __device__ __forceinline__ void cursor_walk(RowCursor &c, const Seg &seg, const 
         int32_t nd = nend - (int32_t)ne0;
         if (seg.hub_len(nd)) nd = 0;   // a hub row has no edges to prefetch
         if (nd > 0) nwin = col[ne0 + (lane < nd ? lane : nd - 1)];
-        nside = side_ok ? xext[nrow * kInLd + side_slot] : 0.0f;
-        if (side_slot2 >= 0) nside2 = side_ok ? xext[nrow * kInLd + side_slot2] : 0.0f;
+        nside = side_ok ? xown[nrow * kInLd + side_slot] : 0.0f;
+        if (side_slot2 >= 0) nside2 = side_ok ? xown[nrow * kInLd + side_slot2] : 0.0f;
     };
     for (int32_t j0 = 0; j0 < c.deg; j0 += 16) {
         const int32_t j1 = j0 + 16;
@@ -453,7 +461,7 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_fwd(InFwdParams p) {
     const int side2 = TM ? aR_slot(n16 & 7) : -1;
     const RowSeg seg{p.rowptr, p.hub.threshold};
     RowCursor cur;
-    cursor_start(cur, seg, p.col, p.xext, row_of(blockIdx.x), aL_slot(n16 & 7), side2, side_ok, lane);
+    cursor_start(cur, seg, p.col, p.xext, p.xown, row_of(blockIdx.x), aL_slot(n16 & 7), side2, side_ok, lane);
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         f4v acc[kInTiles], accT[kInTiles];
 #pragma unroll
@@ -472,7 +480,8 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_fwd(InFwdParams p) {
             const FwdB bfn{cur.side, p.slope, p.H, n16};
             // the backward's alpha of edge (col -> row): gala_gat_in_bwd's formula
             const AlphaB bfnT{cur.side2, p.slope, p.H, n16, kq};
-            cursor_walk(cur, seg, p.col, p.xext, row_of(blk + gridDim.x), aL_slot(n16 & 7), side2, side_ok, lane,
+            cursor_walk(cur, seg, p.col, p.xext, p.xown, row_of(blk + gridDim.x), aL_slot(n16 & 7), side2, side_ok,
+                        lane,
                         [&](const f4v (&xa)[4], const f4v (&xb)[4], int32_t j0, int32_t deg) {
                             mfma_batch(xa, xb, j0, deg, kq, n16, bfn, acc);
                             if (TM) mfma_batch(xa, xb, j0, deg, kq, n16, bfnT, accT);
@@ -521,7 +530,7 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_fwd(InFwdParams p) {
                 const float S = stf[fwd_stash(4, 3, s, h) * 4];
                 const float Sm = stf[fwd_stash(4, 3, s, h + 8) * 4];
                 // REF: 1 / (1e-12 + sum p); T mode: k_gat_in_q's (the sequential row sum)
-                const float qv = TM ? p.xext[row * kInLd + q_slot(h)] : 1.0f / __fadd_rn(S, 1e-12f);
+                const float qv = TM ? p.xown[row * kInLd + q_slot(h)] : 1.0f / __fadd_rn(S, 1e-12f);
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     const int j = 16 * nt + n16;
@@ -535,7 +544,7 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_fwd(InFwdParams p) {
                 if (n16 == 0) {
                     p.q[row * p.H + h] = qv;
                     p.sma[row * p.H + h] = __fmul_rn(qv, Sm);
-                    if (!TM) p.xext[row * kInLd + q_slot(h)] = qv;
+                    if (!TM) p.xown[row * kInLd + q_slot(h)] = qv;
                 }
             }
         }
@@ -546,7 +555,7 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_fwd(InFwdParams p) {
 struct InBwdParams {
     const int32_t *rowptr, *col, *order;   // the transposed pattern
     int64_t n_rows;
-    const float *xext, *dY, *Y, *Ym, *sma;
+    const float *xext, *xown, *dY, *Y, *Ym, *sma;   // xown: as InFwdParams'
     int64_t ldy;
     int32_t fin, H, D;
     float slope;
@@ -595,7 +604,7 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_bwd(InBwdParams p) {
     const bool side_ok = n16 < p.H;
     const RowSeg seg{p.rowptr, p.hub.threshold};
     RowCursor cur;
-    if (!TM) cursor_start(cur, seg, p.col, p.xext, col_of(blockIdx.x), aR_slot(n16 & 7), -1, side_ok, lane);
+    if (!TM) cursor_start(cur, seg, p.col, p.xext, p.xown, col_of(blockIdx.x), aR_slot(n16 & 7), -1, side_ok, lane);
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         f4v acc[kInTiles];
 #pragma unroll
@@ -623,7 +632,7 @@ __global__ __launch_bounds__(kInBlock, 2) void k_gat_in_bwd(InBwdParams p) {
         } else {
             const AlphaB bfn{cur.side, p.slope, p.H, n16, kq};
             const int32_t hub = cur.hub;
-            cursor_walk(cur, seg, p.col, p.xext, col_of(blk + gridDim.x), aR_slot(n16 & 7), -1, side_ok, lane,
+            cursor_walk(cur, seg, p.col, p.xext, p.xown, col_of(blk + gridDim.x), aR_slot(n16 & 7), -1, side_ok, lane,
                         [&](const f4v (&xa)[4], const f4v (&xb)[4], int32_t j0, int32_t deg) {
                             mfma_batch(xa, xb, j0, deg, kq, n16, bfn, acc);
                         });
@@ -716,6 +725,7 @@ __global__ __launch_bounds__(kBlock) void k_gat_in_reduce(const float *part, int
 // row sum (K7) -- into the row's q slots of the extended table.
 // the rows' aR in a compact [n][8] table (78 MB at the Products shape: the q pass's gathers
 // hit the MALL instead of fetching a 128-B line of the 1.25 GB extended table per edge)
+// (n_rows: the TABLE's rows -- the q pass reads art[c] for any column c)
 __global__ __launch_bounds__(kBlock) void k_gat_in_ar(const float *xext, int64_t n_rows, float *ar) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n_rows * 8) ar[i] = xext[(i >> 3) * kInLd + aR_slot((int)(i & 7))];
@@ -748,6 +758,8 @@ __device__ __forceinline__ float q_edge_sum(const int32_t *col, int64_t e0, int6
 }
 
 // thr: rows longer than thr are hub rows, summed by k_gat_in_q_chunks / k_gat_in_q_hub
+// xext (here and in the two kernels below): the table row of row 0 -- these kernels touch the
+// rows' own extended rows only (the gathers go through art)
 __global__ __launch_bounds__(kBlock) void k_gat_in_q(const int32_t *rowptr, const int32_t *col, int64_t n_rows,
                                                      int32_t H, float slope, const float *art, float *xext,
                                                      int32_t thr) {
@@ -793,6 +805,30 @@ __global__ __launch_bounds__(kBlock) void k_gat_in_q_hub(HubSplit hub, int32_t H
     xext[(int64_t)hub.rows[ri] * kInLd + q_slot(h)] = 1.0f / __fadd_rn(S, 1e-12f);
 }
 
+// The q slots of table rows packed to and from [n][H] (a row partition exchanges q of its halo
+// rows, gala.dist.HaloGatInput): one thread per (row, head); rows null: the block of n rows
+// from row0.  A listed row outside the table is skipped.
+__global__ __launch_bounds__(kBlock) void k_gat_in_q_gather(int64_t n, const int32_t *rows, int64_t n_table, int32_t H,
+                                                            const float *xext, float *dst) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int h = (int)(i & 7);
+    const int64_t k = i >> 3;
+    if (k >= n || h >= H) return;
+    const int64_t r = rows[k];
+    dst[k * H + h] = (r >= 0 && r < n_table) ? xext[r * kInLd + q_slot(h)] : 0.0f;
+}
+
+__global__ __launch_bounds__(kBlock) void k_gat_in_q_scatter(int64_t n, const int32_t *rows, int64_t row0,
+                                                             int64_t n_table, int32_t H, const float *src,
+                                                             float *xext) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int h = (int)(i & 7);
+    const int64_t k = i >> 3;
+    if (k >= n || h >= H) return;
+    const int64_t r = rows ? (int64_t)rows[k] : row0 + k;
+    if (r >= 0 && r < n_table) xext[r * kInLd + q_slot(h)] = src[k * H + h];
+}
+
 // The hub rows' pre-pass: one wave per chunk of the plan (a persistent grid, the next chunk's
 // bounds, window and first batch requested while this one is summed), the same batches and B
 // operands as the rows' walk.  MODE 0: the forward's 16 variants (kWsFwd floats per chunk);
@@ -800,7 +836,7 @@ __global__ __launch_bounds__(kBlock) void k_gat_in_q_hub(HubSplit hub, int32_t H
 // layout); 2: the backward over the transposed pattern, its 8 head columns (kWsBwd).
 struct InChunkParams {
     const int32_t *rowptr, *col;
-    const float *xext;
+    const float *xext, *xown;   // xown: as InFwdParams'
     int32_t H;
     float slope;
     HubSplit hub;
@@ -815,14 +851,15 @@ __global__ __launch_bounds__(kBlock, 2) void k_gat_in_chunks(InChunkParams p) {
     const int side = MODE == 2 ? aR_slot(n16 & 7) : aL_slot(n16 & 7), side2 = MODE == 1 ? aR_slot(n16 & 7) : -1;
     const ChunkSeg seg{p.rowptr, p.hub};
     RowCursor cur;
-    cursor_start(cur, seg, p.col, p.xext, g0 < p.hub.n_chunks ? g0 : -1, side, side2, side_ok, lane);
+    cursor_start(cur, seg, p.col, p.xext, p.xown, g0 < p.hub.n_chunks ? g0 : -1, side, side2, side_ok, lane);
     for (int64_t c = g0; c < p.hub.n_chunks; c += gstep) {
         f4v acc[kInTiles], accT[kInTiles];
 #pragma unroll
         for (int t = 0; t < kInTiles; ++t) acc[t] = accT[t] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
         const FwdB bf{cur.side, p.slope, p.H, n16};
         const AlphaB ba{MODE == 2 ? cur.side : cur.side2, p.slope, p.H, n16, kq};
-        cursor_walk(cur, seg, p.col, p.xext, c + gstep < p.hub.n_chunks ? c + gstep : -1, side, side2, side_ok, lane,
+        cursor_walk(cur, seg, p.col, p.xext, p.xown, c + gstep < p.hub.n_chunks ? c + gstep : -1, side, side2, side_ok,
+                    lane,
                     [&](const f4v (&xa)[4], const f4v (&xb)[4], int32_t j0, int32_t deg) {
                         if (MODE == 2) mfma_batch(xa, xb, j0, deg, kq, n16, ba, acc);
                         else mfma_batch(xa, xb, j0, deg, kq, n16, bf, acc);
@@ -848,15 +885,22 @@ int grid_for(int64_t n_rows) {
 
 // need: the floats per chunk this call's pre-pass writes (gala_gat_in_split_ws_cols).  *hub:
 // the device view of A's hub-row plan, threshold INT32_MAX when A has no hub rows.
-int check_in_graph(const gala_csr_t *A, int32_t fin, int32_t heads, int32_t D, int64_t need, HubSplit *hub) {
+// row_base: the table row of A's row 0.  kSquare: the square entry points -- the rectangular
+// path with row_base 0, on a square pattern only.
+constexpr int64_t kSquare = INT64_MIN;
+int check_in_graph(const gala_csr_t *A, int64_t row_base, int32_t fin, int32_t heads, int32_t D, int64_t need,
+                   HubSplit *hub) {
     int st = check_csr(A);
     if (st) return st;
-    if (fin < 1 || heads < 1 || D < 1) return GALA_ERR_INVALID_ARG;
+    const bool square = row_base == kSquare;
+    if (square) row_base = 0;
+    if (fin < 1 || heads < 1 || D < 1 || row_base < 0) return GALA_ERR_INVALID_ARG;
     // the extended row holds at most 100 features and 8 heads; the projection's N = D <= 32
-    // with D / 4 lanes per head in the d_aL dots; one segment, a square pattern
+    // with D / 4 lanes per head in the d_aL dots; one segment; the rows a block of the table's
     if (fin > kInMaxFin || heads > kInMaxHeads || !(D == 4 || D == 8 || D == 16 || D == 32) || A->n_seg != 1 ||
-        A->n_rows != A->n_cols)
+        A->n_rows > A->n_cols || (square && A->n_rows != A->n_cols))
         return GALA_ERR_UNSUPPORTED;
+    if (row_base + A->n_rows > A->n_cols) return GALA_ERR_INVALID_ARG;
     *hub = HubSplit{};
     hub->threshold = INT32_MAX;
     const gala_split_plan_t *plan = A->split;
@@ -892,39 +936,54 @@ extern "C" int gala_gat_in_prep_f32(int64_t n, int32_t fin, const float *Xin, in
 }
 
 namespace {
-int fwd_launch(const gala_csr_t *A, const int32_t *order, int32_t fin, int32_t heads, int32_t D, float slope,
-               float *Xext, const float *W, int64_t ldw, const float *b, float *Y, float *Ym, int64_t ldy, float *q,
-               float *sma, int32_t flags, float *T, void *stream) {
+// T mode's q pass over A's rows (hub rows included), into the rows' own table rows; ar: the
+// compact aR copy of the whole table (8 floats per table row)
+int q_launch(const gala_csr_t *A, int64_t row_base, int32_t heads, float slope, float *Xext, float *ar,
+             const HubSplit &hub, hipStream_t hs) {
+    int st;
+    float *xown = Xext + row_base * kInLd;
+    hipLaunchKernelGGL(k_gat_in_ar, dim3((unsigned)((A->n_cols * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, hs, Xext,
+                       A->n_cols, ar);
+    if ((st = launch_status())) return st;
+    const int64_t groups = (A->n_rows + kBlock / 8 - 1) / (kBlock / 8);
+    hipLaunchKernelGGL(k_gat_in_q, dim3((unsigned)std::min<int64_t>(groups, 8192)), dim3(kBlock), 0, hs, A->rowptr,
+                       A->col, A->n_rows, heads, slope, ar, xown, hub.threshold);
+    if ((st = launch_status())) return st;
+    if (hub.threshold != INT32_MAX) {   // the hub rows' q (the pre-pass's alpha reads q of every gathered row)
+        const int64_t cgroups = (hub.n_chunks + kBlock / 8 - 1) / (kBlock / 8);
+        hipLaunchKernelGGL(k_gat_in_q_chunks, dim3((unsigned)std::min<int64_t>(cgroups, 8192)), dim3(kBlock), 0, hs,
+                           A->rowptr, A->col, hub, heads, slope, ar, xown);
+        if ((st = launch_status())) return st;
+        hipLaunchKernelGGL(k_gat_in_q_hub, dim3((unsigned)((hub.n_rows_split * 8 + kBlock - 1) / kBlock)),
+                           dim3(kBlock), 0, hs, hub, heads, xown);
+        if ((st = launch_status())) return st;
+    }
+    return GALA_OK;
+}
+
+// T (T mode) with qpass: the square form, whose q pass keeps the compact aR copy in T's first
+// 8 n floats until the forward writes T; without: q is in every table row the walk gathers
+int fwd_launch(const gala_csr_t *A, int64_t row_base, const int32_t *order, int32_t fin, int32_t heads, int32_t D,
+               float slope, float *Xext, const float *W, int64_t ldw, const float *b, float *Y, float *Ym, int64_t ldy,
+               float *q, float *sma, int32_t flags, float *T, bool qpass, void *stream) {
     HubSplit hub;
-    int st = check_in_graph(A, fin, heads, D, T ? kWsFwdT : kWsFwd, &hub);
+    int st = check_in_graph(A, row_base, fin, heads, D, T ? kWsFwdT : kWsFwd, &hub);
     if (st) return st;
+    if (row_base == kSquare) row_base = 0;
     if (ldw < fin || ldy < (int64_t)heads * D || (flags & ~GALA_GAT_IN_RELU)) return GALA_ERR_INVALID_ARG;
     if (A->n_rows == 0) return GALA_OK;
     if (!Xext || !W || !Y || !Ym || !q || !sma || ((uintptr_t)Xext & 15) || ((uintptr_t)T & 15))
         return GALA_ERR_INVALID_ARG;
-    InFwdParams p{A->rowptr, A->col, order ? order : (A->split ? A->split->row_order : nullptr), A->n_rows, Xext, W,
-                  b, ldw,
+    float *xown = Xext + row_base * kInLd;
+    InFwdParams p{A->rowptr, A->col, order ? order : (A->split ? A->split->row_order : nullptr), A->n_rows, Xext, xown,
+                  W, b, ldw,
                   fin, heads, D, slope, Y, Ym, q, sma, ldy, (flags & GALA_GAT_IN_RELU) ? 1 : 0, T, hub};
     hipStream_t hs = (hipStream_t)stream;
     const bool hubs = hub.threshold != INT32_MAX;
-    const InChunkParams cp{A->rowptr, A->col, Xext, heads, slope, hub};
+    const InChunkParams cp{A->rowptr, A->col, Xext, xown, heads, slope, hub};
     if (T) {
-        // T's first 8 n floats hold the compact aR table until the forward writes T
-        hipLaunchKernelGGL(k_gat_in_ar, dim3((unsigned)((A->n_rows * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, hs,
-                           Xext, A->n_rows, T);
-        if ((st = launch_status())) return st;
-        const int64_t groups = (A->n_rows + kBlock / 8 - 1) / (kBlock / 8);
-        hipLaunchKernelGGL(k_gat_in_q, dim3((unsigned)std::min<int64_t>(groups, 8192)), dim3(kBlock), 0, hs,
-                           A->rowptr, A->col, A->n_rows, heads, slope, T, Xext, hub.threshold);
-        if ((st = launch_status())) return st;
-        if (hubs) {   // the hub rows' q (the pre-pass's alpha reads q of every gathered row), then their tiles
-            const int64_t cgroups = (hub.n_chunks + kBlock / 8 - 1) / (kBlock / 8);
-            hipLaunchKernelGGL(k_gat_in_q_chunks, dim3((unsigned)std::min<int64_t>(cgroups, 8192)), dim3(kBlock), 0, hs,
-                               A->rowptr, A->col, hub, heads, slope, T, Xext);
-            if ((st = launch_status())) return st;
-            hipLaunchKernelGGL(k_gat_in_q_hub, dim3((unsigned)((hub.n_rows_split * 8 + kBlock - 1) / kBlock)),
-                               dim3(kBlock), 0, hs, hub, heads, Xext);
-            if ((st = launch_status())) return st;
+        if (qpass && (st = q_launch(A, row_base, heads, slope, Xext, T, hub, hs))) return st;
+        if (hubs) {   // the hub rows' tiles
             hipLaunchKernelGGL(k_gat_in_chunks<1>, dim3(chunk_grid(hub.n_chunks)), dim3(kBlock), 0, hs, cp);
             if ((st = launch_status())) return st;
         }
@@ -944,7 +1003,8 @@ extern "C" int gala_gat_in_fwd_f32(const gala_csr_t *A, const int32_t *order, in
                                    float slope,
                                    float *Xext, const float *W, int64_t ldw, const float *b, float *Y, float *Ym,
                                    int64_t ldy, float *q, float *sma, int32_t flags, void *stream) {
-    return fwd_launch(A, order, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags, nullptr, stream);
+    return fwd_launch(A, kSquare, order, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags, nullptr, false,
+                      stream);
 }
 
 extern "C" int gala_gat_in_fwd_t_f32(const gala_csr_t *A, const int32_t *order, int32_t fin, int32_t heads, int32_t D,
@@ -952,7 +1012,61 @@ extern "C" int gala_gat_in_fwd_t_f32(const gala_csr_t *A, const int32_t *order, 
                                      float *Ym, int64_t ldy, float *q, float *sma, int32_t flags, float *T,
                                      void *stream) {
     if (!T) return GALA_ERR_INVALID_ARG;
-    return fwd_launch(A, order, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags, T, stream);
+    return fwd_launch(A, kSquare, order, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags, T, true, stream);
+}
+
+extern "C" int gala_gat_in_fwd_rect_f32(const gala_csr_t *A, int64_t row_base, const int32_t *order, int32_t fin,
+                                        int32_t heads, int32_t D, float slope, float *Xext, const float *W, int64_t ldw,
+                                        const float *b, float *Y, float *Ym, int64_t ldy, float *q, float *sma,
+                                        int32_t flags, void *stream) {
+    if (row_base < 0) return GALA_ERR_INVALID_ARG;
+    return fwd_launch(A, row_base, order, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags, nullptr,
+                      false, stream);
+}
+
+extern "C" int gala_gat_in_fwd_t_rect_f32(const gala_csr_t *A, int64_t row_base, const int32_t *order, int32_t fin,
+                                          int32_t heads, int32_t D, float slope, float *Xext, const float *W,
+                                          int64_t ldw, const float *b, float *Y, float *Ym, int64_t ldy, float *q,
+                                          float *sma, int32_t flags, float *T, void *stream) {
+    if (row_base < 0) return GALA_ERR_INVALID_ARG;
+    if (!T && !(A && A->n_rows == 0)) return GALA_ERR_INVALID_ARG;   // (a rank without rows has no T)
+    return fwd_launch(A, row_base, order, fin, heads, D, slope, Xext, W, ldw, b, Y, Ym, ldy, q, sma, flags, T, false,
+                      stream);
+}
+
+extern "C" int gala_gat_in_q_rect_f32(const gala_csr_t *A, int64_t row_base, int32_t heads, float slope, float *Xext,
+                                      float *ar_scratch, void *stream) {
+    if (row_base < 0) return GALA_ERR_INVALID_ARG;
+    HubSplit hub;
+    // (no Linear here: any supported fin and D pass the shape checks)
+    int st = check_in_graph(A, row_base, 1, heads, 4, kWsFwdT, &hub);
+    if (st) return st;
+    if (A->n_rows == 0) return GALA_OK;
+    if (!Xext || !ar_scratch || ((uintptr_t)Xext & 15)) return GALA_ERR_INVALID_ARG;
+    return q_launch(A, row_base, heads, slope, Xext, ar_scratch, hub, (hipStream_t)stream);
+}
+
+extern "C" int gala_gat_in_q_gather_f32(int64_t n_idx, const int32_t *rows, int64_t n_table, int32_t heads,
+                                        const float *Xext, float *dst, void *stream) {
+    if (n_idx < 0 || n_table < 0 || heads < 1) return GALA_ERR_INVALID_ARG;
+    if (heads > kInMaxHeads) return GALA_ERR_UNSUPPORTED;
+    if (n_idx == 0) return GALA_OK;
+    if (!rows || !Xext || !dst) return GALA_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_gat_in_q_gather, dim3((unsigned)((n_idx * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, n_idx, rows, n_table, heads, Xext, dst);
+    return launch_status();
+}
+
+extern "C" int gala_gat_in_q_scatter_f32(int64_t n, const int32_t *rows, int64_t row0, int64_t n_table, int32_t heads,
+                                         const float *src, float *Xext, void *stream) {
+    if (n < 0 || n_table < 0 || heads < 1) return GALA_ERR_INVALID_ARG;
+    if (!rows && (row0 < 0 || row0 + n > n_table)) return GALA_ERR_INVALID_ARG;
+    if (heads > kInMaxHeads) return GALA_ERR_UNSUPPORTED;
+    if (n == 0) return GALA_OK;
+    if (!src || !Xext) return GALA_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_gat_in_q_scatter, dim3((unsigned)((n * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, n, rows, row0, n_table, heads, src, Xext);
+    return launch_status();
 }
 
 extern "C" int64_t gala_gat_in_split_ws_cols(int32_t mode) {
@@ -971,7 +1085,7 @@ extern "C" int64_t gala_gat_in_bwd_workspace(int32_t heads) {
 
 namespace {
 // AT: the transposed pattern (walked), or null with T: the forward's T tiles of n_rows columns
-int bwd_launch(const gala_csr_t *AT, int64_t n_rows, const int32_t *order, int32_t fin, int32_t heads, int32_t D,
+int bwd_launch(const gala_csr_t *AT, int64_t row_base, int64_t n_rows, const int32_t *order, int32_t fin, int32_t heads, int32_t D,
                float slope, const float *Xext, const float *T, const float *dY, const float *Y, const float *Ym,
                int64_t ldy, const float *sma, float *daL, float *M, void *ws_, int64_t ws_bytes, int32_t flags,
                void *stream) {
@@ -980,7 +1094,8 @@ int bwd_launch(const gala_csr_t *AT, int64_t n_rows, const int32_t *order, int32
     HubSplit hub{};
     hub.threshold = INT32_MAX;
     if (AT) {
-        if ((st = check_in_graph(AT, fin, heads, D, kWsBwd, &hub))) return st;
+        if ((st = check_in_graph(AT, row_base, fin, heads, D, kWsBwd, &hub))) return st;
+        if (row_base == kSquare) row_base = 0;
         n_rows = AT->n_rows;
     } else {
         if (n_rows < 0 || fin < 1 || heads < 1 || D < 1) return GALA_ERR_INVALID_ARG;
@@ -1000,11 +1115,12 @@ int bwd_launch(const gala_csr_t *AT, int64_t n_rows, const int32_t *order, int32
     if (ws_bytes < gala_gat_in_bwd_workspace(heads)) return GALA_ERR_INVALID_ARG;
     const int grid = grid_for(n_rows);
     const int32_t *ord = order ? order : (AT && AT->split ? AT->split->row_order : nullptr);
-    InBwdParams p{AT ? AT->rowptr : nullptr, AT ? AT->col : nullptr, ord, n_rows, Xext, dY, Y, Ym,
+    const float *xown = Xext ? Xext + row_base * kInLd : nullptr;
+    InBwdParams p{AT ? AT->rowptr : nullptr, AT ? AT->col : nullptr, ord, n_rows, Xext, xown, dY, Y, Ym,
                   sma, ldy, fin, heads, D, slope, daL, ws, (flags & GALA_GAT_IN_RELU) ? 1 : 0, T, hub};
     if (hipMemsetAsync(M, 0, outn * sizeof(float), hs) != hipSuccess) return GALA_ERR_HIP;
     if (hub.threshold != INT32_MAX) {   // the hub columns' chunks
-        const InChunkParams cp{AT->rowptr, AT->col, Xext, heads, slope, hub};
+        const InChunkParams cp{AT->rowptr, AT->col, Xext, xown, heads, slope, hub};
         hipLaunchKernelGGL(k_gat_in_chunks<2>, dim3(chunk_grid(hub.n_chunks)), dim3(kBlock), 0, hs, cp);
         if ((st = launch_status())) return st;
     }
@@ -1035,7 +1151,7 @@ extern "C" int gala_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *order, i
                                    int64_t ldy, const float *sma, float *daL, float *M, void *ws_,
                                    int64_t ws_bytes, int32_t flags, void *stream) {
     if (!AT) return GALA_ERR_INVALID_ARG;
-    return bwd_launch(AT, 0, order, fin, heads, D, slope, Xext, nullptr, dY, Y, Ym, ldy, sma, daL, M, ws_, ws_bytes,
+    return bwd_launch(AT, kSquare, 0, order, fin, heads, D, slope, Xext, nullptr, dY, Y, Ym, ldy, sma, daL, M, ws_, ws_bytes,
                       flags, stream);
 }
 
@@ -1043,7 +1159,17 @@ extern "C" int gala_gat_in_bwd_t_f32(int64_t n_rows, const int32_t *order, int32
                                      const float *T, const float *dY, const float *Y, const float *Ym, int64_t ldy,
                                      const float *sma, float *daL, float *M, void *ws_, int64_t ws_bytes,
                                      int32_t flags, void *stream) {
-    return bwd_launch(nullptr, n_rows, order, fin, heads, D, 0.0f, nullptr, T, dY, Y, Ym, ldy, sma, daL, M, ws_,
+    return bwd_launch(nullptr, 0, n_rows, order, fin, heads, D, 0.0f, nullptr, T, dY, Y, Ym, ldy, sma, daL, M, ws_,
+                      ws_bytes, flags, stream);
+}
+
+extern "C" int gala_gat_in_bwd_rect_f32(const gala_csr_t *AT, int64_t row_base, const int32_t *order, int32_t fin,
+                                        int32_t heads, int32_t D, float slope, const float *Xext, const float *dY,
+                                        const float *Y, const float *Ym, int64_t ldy, const float *sma, float *daL,
+                                        float *M, void *ws_, int64_t ws_bytes, int32_t flags, void *stream) {
+    if (row_base < 0) return GALA_ERR_INVALID_ARG;
+    if (!AT) return GALA_ERR_INVALID_ARG;
+    return bwd_launch(AT, row_base, 0, order, fin, heads, D, slope, Xext, nullptr, dY, Y, Ym, ldy, sma, daL, M, ws_,
                       ws_bytes, flags, stream);
 }
 

@@ -110,6 +110,35 @@ class HipBackend:
         full, db = self.ops.dense_grad(X, g.contiguous())
         return _block_diag(full, heads), db
 
+    # -- the GAT layer in input space over a table (gala_gat_in_*_rect_f32; gala.dist.HaloGatInput)
+    gat_in_tmode = True   # the T-mode forward / backward pair exists
+
+    def gat_in_prep(self, X, u, c, heads, xext):
+        return self.ops.gat_in_prep(X, u, c, heads, xext=xext)
+
+    def gat_in_fwd(self, g, xext, W, b, heads, slope, relu, row_base, T=None):
+        """(Y, Ym, q, sma) of g's rows over the table xext; T: the T-mode forward (q already in
+        every gathered row)."""
+        return self.ops.gat_in_fwd(g, xext, W, b, heads, W.shape[1], slope, relu=relu, T=T, row_base=row_base)
+
+    def gat_in_q(self, g, xext, heads, slope, row_base, scratch=None):
+        return self.ops.gat_in_q(g, xext, heads, slope, row_base=row_base, scratch=scratch)
+
+    def gat_in_bwd(self, g, xext, dY, Y, Ym, sma, heads, fin, slope, relu, row_base, T=None):
+        """(d_aL, M) over the local pattern (the walk), or from T."""
+        return self.ops.gat_in_bwd(g, xext, dY, Y, Ym, sma, heads, fin, slope, relu=relu, T=T,
+                                   row_base=None if T is not None else row_base)
+
+    def gat_in_q_gather(self, xext, rows, heads, out=None):
+        return self.ops.gat_in_q_gather(xext, rows, heads, out=out)
+
+    def gat_in_q_scatter(self, xext, src, heads, rows=None, row0=0):
+        return self.ops.gat_in_q_scatter(xext, src, heads, rows=rows, row0=row0)
+
+    def dense_grad(self, X, g):
+        """(g^T X [M, K], sum g [M]) (gala_dense_grad_f32)."""
+        return self.ops.dense_grad(X, g.contiguous())
+
     def empty(self, *shape):
         return torch.empty(shape, device=self.device, dtype=torch.float32)
 
@@ -279,6 +308,61 @@ class CpuBackend:
         _abi.call_cpu("gala_dense_grad_f32", N, K, heads, _hp(X), X.stride(0), _hp(g), heads, _hp(full), _hp(db), 0,
                       _hp(ws), wsb, None)
         return _block_diag(full, heads), db
+
+    # -- the GAT layer in input space over a table (gala_cpu_gat_in_*_rect_f32): the walk only
+    gat_in_tmode = False
+
+    def gat_in_prep(self, X, u, c, heads, xext):
+        _abi.call_cpu("gala_gat_in_prep_f32", X.shape[0], X.shape[1], _hp(X), X.stride(0), heads, _hp(u), _hp(c),
+                      _hp(xext), None)
+        return xext
+
+    def gat_in_fwd(self, g: CpuGraph, xext, W, b, heads, slope, relu, row_base, T=None):
+        if T is not None:
+            raise ValueError("CpuBackend: the input-space layer has no T mode on the host")
+        F, fin = W.shape
+        Y, Ym = torch.empty((g.n_rows, F)), torch.empty((g.n_rows, F))
+        q, sma = torch.empty((g.n_rows, heads)), torch.empty((g.n_rows, heads))
+        _abi.call_cpu("gala_gat_in_fwd_rect_f32", g.csr(), int(row_base), None, fin, heads, F // heads, slope,
+                      _hp(xext), _hp(W), W.stride(0), _hp(b), _hp(Y), _hp(Ym), F, _hp(q), _hp(sma),
+                      _abi.GALA_GAT_IN_RELU if relu else 0, None)
+        return Y, Ym, q, sma
+
+    def gat_in_bwd(self, g: CpuGraph, xext, dY, Y, Ym, sma, heads, fin, slope, relu, row_base, T=None):
+        if T is not None:
+            raise ValueError("CpuBackend: the input-space layer has no T mode on the host")
+        F = dY.shape[1]
+        dY = dY.contiguous()
+        daL = torch.empty((g.n_rows, heads))
+        M = torch.empty((heads, F // heads, fin + 1))
+        wsb = int(_abi.cpu_lib().gala_cpu_gat_in_bwd_workspace(heads))
+        ws = torch.empty(max(wsb // 4, 1))
+        _abi.call_cpu("gala_gat_in_bwd_rect_f32", g.csr(), int(row_base), None, fin, heads, F // heads, slope,
+                      _hp(xext), _hp(dY), _hp(Y), _hp(Ym), F, _hp(sma), _hp(daL), _hp(M), _hp(ws), wsb,
+                      _abi.GALA_GAT_IN_RELU if relu else 0, None)
+        return daL, M
+
+    def gat_in_q_gather(self, xext, rows, heads, out=None):
+        out = torch.empty((rows.shape[0], heads)) if out is None else out
+        _abi.call_cpu("gala_gat_in_q_gather_f32", rows.shape[0], _hp(rows), xext.shape[0], heads, _hp(xext),
+                      _hp(out), None)
+        return out
+
+    def gat_in_q_scatter(self, xext, src, heads, rows=None, row0=0):
+        _abi.call_cpu("gala_gat_in_q_scatter_f32", src.shape[0], _hp(rows), int(row0), xext.shape[0], heads,
+                      _hp(src), _hp(xext), None)
+        return xext
+
+    def dense_grad(self, X, g):
+        g = g.contiguous()
+        N, K = X.shape
+        M = g.shape[1]
+        dW, db = torch.empty((M, K)), torch.empty(M)
+        wsb = int(_abi.cpu_lib().gala_cpu_dense_grad_workspace(N, K, M))
+        ws = torch.empty(max(wsb // 4, 1))
+        _abi.call_cpu("gala_dense_grad_f32", N, K, M, _hp(X), max(X.stride(0), K), _hp(g), M, _hp(dW), _hp(db), 0,
+                      _hp(ws), wsb, None)
+        return dW, db
 
     def empty(self, *shape):
         return torch.empty(shape, dtype=torch.float32)

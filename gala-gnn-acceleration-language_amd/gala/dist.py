@@ -717,3 +717,135 @@ class HaloGatOverlap(HaloGat):
         dW, db = be.head_linear_grads(X, d_aL, H)
         be.head_attn_bwd(d_aL, wR, H, dX)
         return dX, d_aL, dW, db
+
+
+class HaloGatInput:
+    """The GAT layer in INPUT space (gala_gat_in_*: the layer's Linear, its two attention
+    Linears and the REF aggregation from the dataset's features) over a row partition with a
+    halo, for undirected programs on a symmetric graph.  The layer's input carries no gradient
+    and does not change between steps, so the halo's raw input rows are fetched ONCE, here, and
+    every forward runs the prep pass over the rank's whole table [lower halo | own rows | higher
+    halo] (dense: the padded table): the weight-dependent logits aL / aR of the halo rows are
+    recomputed locally.  The one per-step quantity a rank cannot form for a halo row is q, the
+    row's softmax denominator, which the backward's alpha of an edge takes from the gathered
+    row: 4 H bytes per halo row and step, against HaloGat's 4 (2F + H).  On a symmetric graph
+    the rank's own rows of A are its own columns of A^T, so the backward walks the same local
+    pattern.  Every row keeps its CSR edge order and the whole graph's hub-row chunks: Y, Ym, q,
+    sma and d_aL are bit-identical to one GPU; M and G are this rank's partials.
+
+      forward_train(X_own_or_None, W, b, wL, bL, wR, bR, relu) -> Y
+      backward(dY) -> (d_aL, M, (Gw, Gb))    partials: the caller all-reduces the parameter
+                                             gradients (ops.gat_in_param_grads composes them)
+      forward(...) -> Y                      inference: no exchange at all
+    comm None: world 1, every exchange skipped.  The partition must have own_offset() (p2p, or
+    dense with one chunk)."""
+
+    def __init__(self, part: GraphPartition, X_own, heads: int, backend, comm=None, slope: float = 0.2,
+                 tmode: bool = True):
+        import torch
+        self.torch = torch
+        if part.chunks != 1:
+            raise ValueError("HaloGatInput: one halo chunk (the kernels read the whole table)")
+        self.part, self.H, self.be, self.comm, self.slope = part, heads, backend, comm, slope
+        self.fin = int(X_own.shape[1])
+        if X_own.shape[0] != part.n:
+            raise ValueError("HaloGatInput: X_own holds the rank's own input rows")
+        self.tmode = bool(tmode) and backend.gat_in_tmode
+        self.graph = backend.graph(part.graph, split=part.split_threshold)
+        self.x0 = part.own_offset()
+        dev = backend.device
+        if comm is None:
+            self.exchange = None
+        elif part.halo_mode == "p2p":
+            self.exchange = HaloExchange(part, comm, dev)
+        else:
+            self.exchange = DenseHalo(part, comm)
+        dense = part.halo_mode == "dense" and part.world > 1
+        self.Xs = backend.empty(part.n_cols, self.fin)          # the raw input rows, fetched once
+        self.Qs = backend.empty(part.n_cols, heads)             # q of the table rows (the exchange's buffer)
+        self.xext = backend.empty(part.n_cols, 128)
+        if dense:                                               # padding rows: keep the tables finite
+            self.Xs.zero_()
+            self.Qs.zero_()
+        self.own_idx = torch.arange(self.x0, self.x0 + part.n, dtype=torch.int32, device=dev)
+        self.T = backend.empty(part.n, 896) if self.tmode else None
+        # the q pass's compact aR copy: 8 floats per TABLE row; T's storage when it is that large
+        self.scratch = None
+        if self.tmode and 896 * part.n < 8 * part.n_cols:
+            self.scratch = backend.empty(8 * part.n_cols)
+        self._set_own(X_own)
+        self._wait([w for works in (self.exchange.start(self.Xs) if self.exchange else []) for w in works])
+        self.saved = None
+
+    def _set_own(self, X):
+        own = self.Xs[self.x0:self.x0 + self.part.n]
+        if X is not None and X.data_ptr() != own.data_ptr():
+            own.copy_(X)
+
+    @staticmethod
+    def _wait(works):
+        for w in works:
+            if w is not None:
+                w.wait()
+
+    def _prep(self, X, W, b, wL, bL, wR, bR):
+        from . import ops
+        self._set_own(X)     # (the same rows as at setup: the halo copies on the peers are not refreshed)
+        u, c = ops.gat_in_compose(W, b, wL, bL, wR, bR, self.H)
+        self.be.gat_in_prep(self.Xs, u, c, self.H, self.xext)
+
+    def _exchange_q(self):
+        """q of the own rows (in the table) -> the peers' tables; q of the halo rows -> this table."""
+        be, part, H = self.be, self.part, self.H
+        if self.exchange is None:
+            return
+        if part.n:
+            be.gat_in_q_gather(self.xext, self.own_idx, H, out=self.Qs[self.x0:self.x0 + part.n])
+        self._wait([w for works in self.exchange.start(self.Qs) for w in works])
+        if part.halo_mode == "p2p":      # the two halo blocks around the own rows
+            for a, e in ((0, self.x0), (self.x0 + part.n, part.n_cols)):
+                if e > a:
+                    be.gat_in_q_scatter(self.xext, self.Qs[a:e], H, row0=a)
+        else:                            # the whole padded table (the own rows get their own q back)
+            be.gat_in_q_scatter(self.xext, self.Qs, H, row0=0)
+
+    def forward_train(self, X, W, b, wL, bL, wR, bR, relu=False):
+        be, H = self.be, self.H
+        self._prep(X, W, b, wL, bL, wR, bR)
+        if self.tmode:
+            be.gat_in_q(self.graph, self.xext, H, self.slope, self.x0,
+                        scratch=self.T.view(-1) if self.scratch is None else self.scratch)
+            self._exchange_q()
+            Y, Ym, q, sma = be.gat_in_fwd(self.graph, self.xext, W, b, H, self.slope, relu, self.x0, T=self.T)
+        else:
+            Y, Ym, q, sma = be.gat_in_fwd(self.graph, self.xext, W, b, H, self.slope, relu, self.x0)
+            self._exchange_q()
+        self.saved = (Y, Ym, q, sma, relu)
+        return Y
+
+    def forward(self, X, W, b, wL, bL, wR, bR, relu=False):
+        """Inference: prep and the walk forward."""
+        self._prep(X, W, b, wL, bL, wR, bR)
+        return self.be.gat_in_fwd(self.graph, self.xext, W, b, self.H, self.slope, relu, self.x0)[0]
+
+    def backward(self, dY):
+        if self.saved is None:
+            raise RuntimeError("HaloGatInput.backward: no forward_train to take the row statistics from")
+        Y, Ym, q, sma, relu = self.saved
+        be, n = self.be, self.part.n
+        daL, M = be.gat_in_bwd(self.graph, self.xext, dY, Y, Ym, sma, self.H, self.fin, self.slope, relu, self.x0,
+                               T=self.T if self.tmode else None)
+        if n:
+            Gw, Gb = be.dense_grad(self.Xs[self.x0:self.x0 + n], daL)
+        else:
+            Gw, Gb = be.empty(self.H, self.fin).zero_(), be.empty(self.H).zero_()
+        return daL, M, (Gw, Gb)
+
+    def halo_bytes(self) -> int:
+        """Bytes of q this rank needs per forward + backward: 4 H per halo row (what the p2p
+        exchange moves; the dense all-gather moves the padded table, part.halo_bytes(H))."""
+        return 4 * self.H * self.part.n_halo_rows if self.part.world > 1 else 0
+
+    def setup_bytes(self) -> int:
+        """Bytes received once, at setup: the halo's raw input rows."""
+        return self.part.halo_bytes(self.fin) if self.part.world > 1 else 0

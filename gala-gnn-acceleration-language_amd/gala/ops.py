@@ -577,11 +577,15 @@ def _gat_in_ws_cols(g: DeviceGraph, mode: int) -> int:
     return int(_abi.lib().gala_gat_in_split_ws_cols(mode)) if g.split_rows > 0 else 0
 
 
-def gat_in_fwd(g: DeviceGraph, xext, W, b, heads, fin, slope=0.2, order=None, relu=False, T=None, Y=None, Ym=None):
+def gat_in_fwd(g: DeviceGraph, xext, W, b, heads, fin, slope=0.2, order=None, relu=False, T=None, Y=None, Ym=None,
+               row_base=None):
     """gala_gat_in_fwd_f32: (Y, Ym, q, sma); writes q into xext.  order: int32 row order.
     T ([N, 896], symmetric g only): gala_gat_in_fwd_t_f32, which also forms the backward's
     per-column aggregates there.  Y, Ym (optional outputs): [N, H*D] with unit column stride
-    and one row stride, e.g. column views of wider buffers; W likewise (ldw = W.stride(0))."""
+    and one row stride, e.g. column views of wider buffers; W likewise (ldw = W.stride(0)).
+    row_base (an int): the rectangular forms over a table xext [g.n_cols, 128] whose row
+    row_base + r is g's row r (gala_gat_in_fwd_rect_f32; with T gala_gat_in_fwd_t_rect_f32, which
+    runs no q pass: gat_in_q first, and q of every gathered row in the table)."""
     F = W.shape[0]
     D = F // heads
     if Y is None:
@@ -593,23 +597,67 @@ def gat_in_fwd(g: DeviceGraph, xext, W, b, heads, fin, slope=0.2, order=None, re
             raise ValueError(f"gat_in_fwd: {name} must be float32 [{g.n_rows}, {F}] with unit column stride")
     if Ym.stride(0) != Y.stride(0) or (fin > 1 and W.stride(1) != 1):
         raise ValueError("gat_in_fwd: Y and Ym share one row stride; W has unit column stride")
+    if row_base is not None and tuple(xext.shape) != (g.n_cols, 128):
+        raise ValueError(f"gat_in_fwd: the table must be [{g.n_cols}, 128]")
     ldy = max(Y.stride(0), F)  # (empty tensors report any stride)
     q = torch.empty(g.n_rows, heads, device=W.device, dtype=torch.float32)
     sma = torch.empty_like(q)
     flags = _abi.GALA_GAT_IN_RELU if relu else 0
     csr = g.csr(_gat_in_ws_cols(g, _abi.GALA_GAT_IN_WS_FWD if T is None else _abi.GALA_GAT_IN_WS_FWD_T))
+    base = () if row_base is None else (int(row_base),)
+    rect = "" if row_base is None else "rect_"
     if T is None:
-        _abi.call("gala_gat_in_fwd_f32", csr, _dp(order), fin, heads, D, slope, _dp(xext), _dp(W), W.stride(0),
-                  _dp(b), _dp(Y), _dp(Ym), ldy, _dp(q), _dp(sma), flags, _stream())
+        _abi.call(f"gala_gat_in_fwd_{rect}f32", csr, *base, _dp(order), fin, heads, D, slope, _dp(xext), _dp(W),
+                  W.stride(0), _dp(b), _dp(Y), _dp(Ym), ldy, _dp(q), _dp(sma), flags, _stream())
     else:
-        _abi.call("gala_gat_in_fwd_t_f32", csr, _dp(order), fin, heads, D, slope, _dp(xext), _dp(W),
+        _abi.call(f"gala_gat_in_fwd_t_{rect}f32", csr, *base, _dp(order), fin, heads, D, slope, _dp(xext), _dp(W),
                   W.stride(0), _dp(b), _dp(Y), _dp(Ym), ldy, _dp(q), _dp(sma), flags, _dp(T), _stream())
     return Y, Ym, q, sma
 
 
-def gat_in_bwd(gT: DeviceGraph, xext, dY, Y, Ym, sma, heads, fin, slope=0.2, order=None, relu=False, T=None):
+def gat_in_q(g: DeviceGraph, xext, heads, slope=0.2, row_base=0, scratch=None):
+    """gala_gat_in_q_rect_f32: T mode's q pass over g's rows (hub rows included), written into
+    the own rows of the table xext [g.n_cols, 128].  scratch: 8 * g.n_cols floats (the compact
+    aR copy; T's storage when it is that large)."""
+    if tuple(xext.shape) != (g.n_cols, 128):
+        raise ValueError(f"gat_in_q: the table must be [{g.n_cols}, 128]")
+    if scratch is None:
+        scratch = torch.empty(max(8 * g.n_cols, 1), device=xext.device, dtype=torch.float32)
+    if scratch.numel() < 8 * g.n_cols or not scratch.is_contiguous():
+        raise ValueError("gat_in_q: scratch holds 8 floats per table row")
+    csr = g.csr(_gat_in_ws_cols(g, _abi.GALA_GAT_IN_WS_FWD_T))
+    _abi.call("gala_gat_in_q_rect_f32", csr, int(row_base), heads, slope, _dp(xext), _dp(scratch), _stream())
+    return xext
+
+
+def gat_in_q_gather(xext, rows, heads, out=None):
+    """gala_gat_in_q_gather_f32: [len(rows), heads] = the q slots of the table rows `rows` (int32)."""
+    n = int(rows.shape[0])
+    out = torch.empty(n, heads, device=xext.device, dtype=torch.float32) if out is None else out
+    if tuple(out.shape) != (n, heads) or not out.is_contiguous() or rows.dtype != torch.int32:
+        raise ValueError("gat_in_q_gather: rows int32, out a contiguous [len(rows), heads]")
+    _abi.call("gala_gat_in_q_gather_f32", n, _dp(rows), xext.shape[0], heads, _dp(xext), _dp(out), _stream())
+    return out
+
+
+def gat_in_q_scatter(xext, src, heads, rows=None, row0=0):
+    """gala_gat_in_q_scatter_f32: the q slots of the table rows `rows` (int32), or of the block
+    of src.shape[0] rows from row0, = src [n, heads]."""
+    n = int(src.shape[0])
+    if tuple(src.shape) != (n, heads) or not src.is_contiguous() or (rows is not None and (
+            rows.dtype != torch.int32 or rows.shape[0] != n)):
+        raise ValueError("gat_in_q_scatter: src a contiguous [n, heads], rows int32 [n]")
+    _abi.call("gala_gat_in_q_scatter_f32", n, _dp(rows), int(row0), xext.shape[0], heads, _dp(src), _dp(xext),
+              _stream())
+    return xext
+
+
+def gat_in_bwd(gT: DeviceGraph, xext, dY, Y, Ym, sma, heads, fin, slope=0.2, order=None, relu=False, T=None,
+               row_base=None):
     """gala_gat_in_bwd_f32 over the transposed pattern gT: (d_aL [N, H], M [H, D, fin + 1]);
-    with T (the T-mode forward's), gala_gat_in_bwd_t_f32 (no walk over the pattern)."""
+    with T (the T-mode forward's), gala_gat_in_bwd_t_f32 (no walk over the pattern).  row_base
+    (an int): gala_gat_in_bwd_rect_f32 over the table xext [gT.n_cols, 128] (see gat_in_fwd); T
+    mode needs none, it reads row-local arrays only."""
     F = dY.shape[1]
     D = F // heads
     n = dY.shape[0]
@@ -624,12 +672,32 @@ def gat_in_bwd(gT: DeviceGraph, xext, dY, Y, Ym, sma, heads, fin, slope=0.2, ord
     flags = _abi.GALA_GAT_IN_RELU if relu else 0
     if T is None:
         csr = gT.csr(_gat_in_ws_cols(gT, _abi.GALA_GAT_IN_WS_BWD))
-        _abi.call("gala_gat_in_bwd_f32", csr, _dp(order), fin, heads, D, slope, _dp(xext), _dp(dY), _dp(Y),
-                  _dp(Ym), ldy, _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
+        if row_base is None:
+            _abi.call("gala_gat_in_bwd_f32", csr, _dp(order), fin, heads, D, slope, _dp(xext), _dp(dY), _dp(Y),
+                      _dp(Ym), ldy, _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
+        else:
+            if tuple(xext.shape) != (gT.n_cols, 128) or n != gT.n_rows:
+                raise ValueError(f"gat_in_bwd: the table must be [{gT.n_cols}, 128], dY of {gT.n_rows} rows")
+            _abi.call("gala_gat_in_bwd_rect_f32", csr, int(row_base), _dp(order), fin, heads, D, slope, _dp(xext),
+                      _dp(dY), _dp(Y), _dp(Ym), ldy, _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
     else:
         _abi.call("gala_gat_in_bwd_t_f32", n, _dp(order), fin, heads, D, _dp(T), _dp(dY), _dp(Y), _dp(Ym), ldy,
                   _dp(sma), _dp(daL), _dp(M), _dp(ws), wsb, flags, _stream())
     return daL, M
+
+
+def gat_in_param_grads(M, Gw, Gb, W, b, wL, wR, heads):
+    """The six parameter gradients of the input-space layer from M [H, D, fin + 1] and
+    G = d_aL^T [X, 1] (Gw [H, fin], Gb [H]) -- linear in (M, Gw, Gb), so partials of a row
+    partition may be composed per rank and summed, or summed first (REF: d aR = d aL)."""
+    F, fin = W.shape
+    H, D = heads, F // heads
+    sLR = wL.reshape(H, D) + wR.reshape(H, D)
+    bb = b.reshape(H, D) if b is not None else torch.zeros(H, D, device=W.device)
+    dw = (W.reshape(H, D, fin) * Gw.unsqueeze(1)).sum(2) + bb * Gb.unsqueeze(1)
+    return dict(dW=(M[:, :, :fin] + sLR.unsqueeze(2) * Gw.unsqueeze(1)).reshape(F, fin),
+                db=(M[:, :, fin] + sLR * Gb.unsqueeze(1)).reshape(F), dwL=dw.reshape(-1), dwR=dw.reshape(-1),
+                dbL=Gb, dbR=Gb)
 
 
 def degree_order(rowptr):
@@ -681,10 +749,5 @@ def gat_input_layer(g: DeviceGraph, X, W, b, wL, bL, wR, bR, heads, slope=0.2, d
     daL, M = gat_in_bwd(g if gT is None else gT, xext, dY, Y, Ym, sma, heads, fin, slope,
                         order=order if gT is None else order_t, relu=relu, T=T)
     Gw, Gb = dense_grad(X, daL)
-    sLR = wL.reshape(H, D) + wR.reshape(H, D)
-    bb = b.reshape(H, D) if b is not None else torch.zeros(H, D, device=W.device)
-    dw = (W.reshape(H, D, fin) * Gw.unsqueeze(1)).sum(2) + bb * Gb.unsqueeze(1)
-    out.update(daL=daL, M=M, G=Gw, dW=(M[:, :, :fin] + sLR.unsqueeze(2) * Gw.unsqueeze(1)).reshape(F, fin),
-               db=(M[:, :, fin] + sLR * Gb.unsqueeze(1)).reshape(F), dwL=dw.reshape(-1), dwR=dw.reshape(-1),
-               dbL=Gb, dbR=Gb)
+    out.update(daL=daL, M=M, G=Gw, **gat_in_param_grads(M, Gw, Gb, W, b, wL, wR, heads))
     return out

@@ -152,6 +152,21 @@ int gala_cpu_gat_in_bwd_f32(const gala_csr_t *AT, const int32_t *order, int32_t 
                             const float *Xext, const float *dY, const float *Y, const float *Ym,
                             int64_t ldy, const float *sma, float *daL, float *M, void *ws,
                             int64_t ws_bytes, int32_t flags, void *stream);
+/* The rectangular forms (gala_gat_in_*_rect_f32: A's rows a block of a table, row r's own
+ * extended row at row_base + r) and the q pack / unpack; the host has the walk only, no T
+ * mode.  The same sums in the same order as the square twins, which are these at row_base 0. */
+int gala_cpu_gat_in_fwd_rect_f32(const gala_csr_t *A, int64_t row_base, const int32_t *order, int32_t fin,
+                                 int32_t heads, int32_t D, float slope, float *Xext, const float *W, int64_t ldw,
+                                 const float *b, float *Y, float *Ym, int64_t ldy, float *q, float *sma,
+                                 int32_t flags, void *stream);
+int gala_cpu_gat_in_bwd_rect_f32(const gala_csr_t *AT, int64_t row_base, const int32_t *order, int32_t fin,
+                                 int32_t heads, int32_t D, float slope, const float *Xext, const float *dY,
+                                 const float *Y, const float *Ym, int64_t ldy, const float *sma, float *daL,
+                                 float *M, void *ws, int64_t ws_bytes, int32_t flags, void *stream);
+int gala_cpu_gat_in_q_gather_f32(int64_t n_idx, const int32_t *rows, int64_t n_table, int32_t heads,
+                                 const float *Xext, float *dst, void *stream);
+int gala_cpu_gat_in_q_scatter_f32(int64_t n, const int32_t *rows, int64_t row0, int64_t n_table, int32_t heads,
+                                  const float *src, float *Xext, void *stream);
 
 #ifdef __cplusplus
 }

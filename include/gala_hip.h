@@ -579,7 +579,8 @@ int gala_head_attn_bwd_f32(int64_t n_rows, int32_t F, int32_t heads, const float
  *     gradient of relu(Y), masked by relu(Y) > 0 (torch's threshold_backward); the d_aL dots
  *     <dY, Y> are then the same sums over relu(Y).
  * Limits (else GALA_ERR_UNSUPPORTED, callers keep the statistics pair): fin <= 100, heads
- * <= 8, D in {4, 8, 16, 32}, one segment, a square pattern, and, when A->split (AT->split) has
+ * <= 8, D in {4, 8, 16, 32}, one segment, a square pattern (the *_rect_* forms below: n_rows
+ * <= n_cols), and, when A->split (AT->split) has
  * hub rows, a chunk size that is a positive multiple of 64.  Sums are regrouped (the matrix
  * cores sum four edges per step; the input-space association): fp32 rounding of the
  * reference, checked at 1e-4.
@@ -622,6 +623,45 @@ int gala_gat_in_bwd_t_f32(int64_t n_rows, const int32_t *order, int32_t fin, int
                           const float *T, const float *dY, const float *Y, const float *Ym, int64_t ldy,
                           const float *sma, float *daL, float *M, void *ws, int64_t ws_bytes, int32_t flags,
                           void *stream);
+/* The rectangular forms (additive; ABI 6 still): A's rows are a block of a TABLE of extended rows
+ * that A's columns index -- a rank of a row partition, whose table is [lower halo | own rows |
+ * higher halo] (gala.dist.HaloGatInput).  A has n_rows <= n_cols, Xext is [A->n_cols][128], and
+ * row r's own extended row (its aL / aR, and q written or read) is table row row_base + r; Y, Ym,
+ * q, sma, d_aL, dY and T are indexed by r as before, and a plan's hub rows are A's rows.  The
+ * four square entry points above are these with row_base 0 on a pattern with n_rows == n_cols,
+ * bit for bit.  Status, nothing launched: row_base < 0 or row_base + n_rows > n_cols
+ * GALA_ERR_INVALID_ARG; n_rows > n_cols GALA_ERR_UNSUPPORTED; otherwise as the square forms.
+ *   gala_gat_in_fwd_rect_f32 / gala_gat_in_bwd_rect_f32: the walk.  On a symmetric global graph
+ *     a rank's own rows of A are its own columns of A^T, so the backward takes the same local
+ *     pattern; it reads q of every gathered table row, so q of the halo rows must be in the
+ *     table first (the forward wrote q of the own rows only).
+ *   gala_gat_in_q_rect_f32: T mode's q pass over A's rows, hub rows included, into the own table
+ *     rows.  ar_scratch: 8 * n_cols floats (the compact aR copy of the whole table); it may be
+ *     T's storage when that is large enough.  The plan's workspace: GALA_GAT_IN_WS_FWD_T.
+ *   gala_gat_in_fwd_t_rect_f32: the T-mode forward WITHOUT a q pass: q must be present in every
+ *     table row the walk gathers (own rows: gala_gat_in_q_rect_f32; halo rows: received).  T
+ *     [n_rows][896]; gala_gat_in_bwd_t_f32 then serves unchanged (row-local arrays only).
+ *   gala_gat_in_q_gather_f32: dst [n_idx][heads] = the q slots of the table rows rows[i] (int32);
+ *   gala_gat_in_q_scatter_f32: the q slots of table rows rows[i], or with rows NULL of the block
+ *     row0 .. row0 + n - 1, = src [n][heads].  n_table: the table's rows -- a block outside it is
+ *     GALA_ERR_INVALID_ARG, a listed row outside it is skipped (the gather stores 0). */
+int gala_gat_in_fwd_rect_f32(const gala_csr_t *A, int64_t row_base, const int32_t *order, int32_t fin, int32_t heads,
+                             int32_t D, float slope, float *Xext, const float *W, int64_t ldw, const float *b,
+                             float *Y, float *Ym, int64_t ldy, float *q, float *sma, int32_t flags, void *stream);
+int gala_gat_in_q_rect_f32(const gala_csr_t *A, int64_t row_base, int32_t heads, float slope, float *Xext,
+                           float *ar_scratch, void *stream);
+int gala_gat_in_fwd_t_rect_f32(const gala_csr_t *A, int64_t row_base, const int32_t *order, int32_t fin, int32_t heads,
+                               int32_t D, float slope, float *Xext, const float *W, int64_t ldw, const float *b,
+                               float *Y, float *Ym, int64_t ldy, float *q, float *sma, int32_t flags, float *T,
+                               void *stream);
+int gala_gat_in_bwd_rect_f32(const gala_csr_t *AT, int64_t row_base, const int32_t *order, int32_t fin, int32_t heads,
+                             int32_t D, float slope, const float *Xext, const float *dY, const float *Y,
+                             const float *Ym, int64_t ldy, const float *sma, float *daL, float *M, void *ws,
+                             int64_t ws_bytes, int32_t flags, void *stream);
+int gala_gat_in_q_gather_f32(int64_t n_idx, const int32_t *rows, int64_t n_table, int32_t heads, const float *Xext,
+                             float *dst, void *stream);
+int gala_gat_in_q_scatter_f32(int64_t n, const int32_t *rows, int64_t row0, int64_t n_table, int32_t heads,
+                              const float *src, float *Xext, void *stream);
 
 /* dst[i*heads + h] = src[perm[i]*heads + h]  (edge-value permutation for transposed graphs) */
 int gala_edge_permute_f32(const int32_t *perm, const float *src, int64_t n, int32_t heads,

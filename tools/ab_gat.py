@@ -27,7 +27,9 @@ from gala import _abi, ops  # noqa: E402
 def load(path):
     L = ctypes.CDLL(path)
     for name, (res, args) in _abi.SIGNATURES.items():
-        fn = getattr(L, name)
+        fn = getattr(L, name, None)
+        if fn is None:   # an older build of the same ABI version: entry points added since are absent
+            continue
         fn.restype, fn.argtypes = res, args
     assert L.gala_abi_version() == _abi.ABI_VERSION, path
     return L
