@@ -610,8 +610,13 @@ class HaloGat:
         self._wait(ar_works)
         self._wait(works)
         linear = linear and wR is not None
+        # the kernel reads the rows' own dY and the table with one vector width: the own block of
+        # a table whose rows are no multiple of 16 bytes (F = 7) may start off that alignment
+        rows = self.own_rows("dY")
+        if rows.data_ptr() % 16 != self.dYs.data_ptr() % 16:
+            rows = rows.clone()
         # with the Linear: dX += d_aR wR in the kernel's store (REF: d_aR = d_aL)
-        dX, d_aL = self.be.gat_bwd_stats_table(self.graph, aL, self.As, self.dYs, self.own_rows("dY"), q, Y, Ym,
+        dX, d_aL = self.be.gat_bwd_stats_table(self.graph, aL, self.As, self.dYs, rows, q, Y, Ym,
                                                sma, H, self.slope, wR=wR if linear else None)
         d_aL = d_aL.view(n, H)
         if not linear:
@@ -773,6 +778,7 @@ class HaloGatInput:
         self.scratch = None
         if self.tmode and 896 * part.n < 8 * part.n_cols:
             self.scratch = backend.empty(8 * part.n_cols)
+        self.q_exchanges = 0     # q exchanges run so far (forward_train at world > 1; never forward)
         self._set_own(X_own)
         self._wait([w for works in (self.exchange.start(self.Xs) if self.exchange else []) for w in works])
         self.saved = None
@@ -799,6 +805,7 @@ class HaloGatInput:
         be, part, H = self.be, self.part, self.H
         if self.exchange is None:
             return
+        self.q_exchanges += 1
         if part.n:
             be.gat_in_q_gather(self.xext, self.own_idx, H, out=self.Qs[self.x0:self.x0 + part.n])
         self._wait([w for works in self.exchange.start(self.Qs) for w in works])

@@ -36,6 +36,15 @@ gala.cu.  This runtime executes the same post-pass IR (galac --ir-json) instead:
     that Linear's gradients) -- gala/dist.py HaloGat on the halo layout (the one-GPU kernels
     over a gathered table: bit-identical to one rank), VertexCutGat on the vertex cut;
     per-head attention Linears (gat_heads) are the block-diagonal `HeadLinear`.
+  * a GAT program's FIRST layer -- res = ffn(input features), its two attention Linears of res
+    and the aggregation, config 3's layer 1 -- runs in INPUT space on the halo layout
+    (plan_input_layers + input_layer_eligible; gala/dist.py HaloGatInput, the gala_gat_in_*
+    kernels): one autograd op that gathers the dataset's fin-float rows instead of the Linear's
+    H*D-float output, fetches the halo's input rows once and exchanges 4 H bytes of q per halo
+    row and step; its row outputs are bit-identical to one rank, and forwards under
+    torch.no_grad() (--eval) run no exchange.  GALA_GAT_INPUT=0 in the environment (the
+    operator mirror's switch) keeps the three ops and HaloGat; so does every program or layout
+    the predicate refuses.  The summary's `gat_layers` says which layer each GAT node ran.
 Training subgraphs (graph g > 0) run on the whole graph: they only drop rows no training
 row depends on, so the training rows' values are unchanged.  The column-tiled layout
 (col_tile) is a single-device layout and is not used.
@@ -216,6 +225,139 @@ class _VcutGat(torch.autograd.Function):
         dX, d_aL = ctx.layer.backward(dy.contiguous())
         return d_aL, d_aL.clone(), dX, None
 
+class _GatInputLayer(torch.autograd.Function):
+    """A GAT program's first layer in input space over ranks (gala.dist.HaloGatInput): the FFN of
+    the dataset's features, its two attention Linears and the REF aggregation (optionally the
+    ReLU after it) as one op.  Inputs: the FFN's W [H*D, fin], b [H*D] and the attention
+    Linears' wL, bL, wR, bR; the rank's own input rows live in `layer` (they carry no gradient,
+    so they are no input of the op).  Backward: HaloGatInput.backward's d_aL-side partials M and
+    (Gw, Gb) of this rank's rows composed into the six parameter gradients
+    (ops.gat_in_param_grads, linear in the partials); the program's per-weight all-reduce sums
+    them over the ranks like every other weight gradient.  Nothing but the four parameter
+    tensors the composition reads is saved: the row statistics, the table xext and T stay in
+    the layer object (T mode's backward reads no xext, and none is duplicated for it)."""
+
+    @staticmethod
+    def forward(ctx, W, b, wL, bL, wR, bR, layer, relu):
+        ctx.layer = layer
+        ctx.save_for_backward(W, b, wL, wR)
+        return layer.forward_train(None, *(t.detach().contiguous() for t in (W, b, wL, bL, wR, bR)), relu=relu)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import ops
+        W, b, wL, wR = ctx.saved_tensors
+        dY = dy.contiguous()
+        if dY.data_ptr() % 16:   # the kernels read dY rows as float4: a contiguous view at an
+            dY = dY.clone()      # unaligned storage offset is copied to a fresh allocation
+        _, M, (Gw, Gb) = ctx.layer.backward(dY)
+        g = ops.gat_in_param_grads(M, Gw, Gb, W.detach(), b.detach(), wL.detach(), wR.detach(), ctx.layer.H)
+        # REF: d aR = d aL; the two attention Linears get separate tensors (their .grad are
+        # all-reduced and stepped in place, one by one)
+        return (g["dW"], g["db"], g["dwL"].reshape(wL.shape), g["dbL"].reshape(-1),
+                g["dwR"].reshape(wR.shape).clone(), g["dbR"].reshape(-1).clone(), None, None)
+
+
+def plan_input_layers(ir: dict) -> dict:
+    """The GAT_AGGREGATE nodes of the post-pass IR that are a first layer in input space, as
+    galac's emitter finds them (compiler/emit.cpp plan_input_layers):
+    {GAT node's value: {"ffn", "attn", "relu"}} (the values of the FFN, of the destination
+    logit and of the folded ReLU, or None).  A node matches when its feature operand is an FFN
+    of the program's INPUT; its destination logit is an FFN(out=1) -- per head: a HeadLinear --
+    of that FFN's output; its source logit is its own attention Linear of the same value
+    (`weight` set, operand 1 absent); the FFN's output has exactly those two readers and the
+    logit one; none of the three is hoisted.  A RELU that is the node's only reader, not
+    hoisted and not the program's output, is folded in.  The IR keeps its nodes: this is an
+    execution-time fusion."""
+    nodes = ir["nodes"]
+    by_out = {nd["out"]: nd for nd in nodes}
+    weights = {w["name"]: w for w in ir["weights"]}
+
+    def uses(v):
+        return [nd for nd in nodes if v in nd["in"]]
+
+    plan = {}
+    for nd in nodes:
+        if nd["op"] != "GAT_AGGREGATE" or not nd["weight"] or nd.get("hoisted") or len(nd["in"]) < 3:
+            continue
+        if nd["in"][0] < 0 or nd["in"][2] < 0 or nd["in"][1] >= 0:
+            continue
+        x, a = by_out.get(nd["in"][2]), by_out.get(nd["in"][0])
+        if x is None or a is None or x["op"] != "FFN" or a["op"] != "FFN" or x.get("hoisted") or a.get("hoisted"):
+            continue
+        if not x["weight"] or not a["weight"] or by_out.get(x["in"][0], {}).get("op") != "INPUT":
+            continue
+        wx, wa, wr = weights[x["weight"]], weights[a["weight"]], weights[nd["weight"]]
+        if any(w["type"] != "linear" for w in (wx, wa, wr)) or int(wx.get("heads", 1)) > 1:
+            continue
+        if wa["out"] != 1 or wr["out"] != 1 or a["in"][0] != nd["in"][2]:
+            continue
+        if len(uses(nd["in"][2])) != 2 or len(uses(nd["in"][0])) != 1:
+            continue
+        relu = None
+        uy = uses(nd["out"])
+        if len(uy) == 1 and uy[0]["op"] == "RELU" and not uy[0].get("hoisted") and nd["out"] != ir["output"]:
+            relu = uy[0]["out"]
+        plan[nd["out"]] = {"ffn": x["out"], "attn": a["out"], "relu": relu}
+    return plan
+
+
+def gat_input_enabled() -> bool:
+    """GALA_GAT_INPUT=0 (the operator mirror's switch, host/gala_torch.cpp) keeps the three ops."""
+    return not os.environ.get("GALA_GAT_INPUT", "").startswith("0")
+
+
+def input_layer_eligible(ir: dict, nd: dict, plan: dict, layout_mode: str, part, symmetric) -> bool:
+    """Whether the GAT_AGGREGATE node `nd` runs as the input-space layer (_GatInputLayer over
+    gala.dist.HaloGatInput).  Every condition:
+      * plan_input_layers matched the node (`plan`, that function's result);
+      * GALA_GAT_INPUT=0 is not set in the environment;
+      * the kernels' limits: 1 <= fin <= 100 input features, 1..8 heads, D = out /
+        heads in {4, 8, 16, 32}, and fin < H*D -- the input row is narrower than the Linear's
+        output, which is the point -- with both attention Linears of H heads over H*D features;
+      * REF softmax (sched gat_mode == 0);
+      * an undirected program (sched undirected) on a graph whose pattern equals its transpose
+        (`symmetric`: a bool, or a () -> bool evaluated only when everything else holds; the
+        backward walks the rank's own rows as its columns of A^T);
+      * no kernel sampling (sched kernel_sample == 0);
+      * layout "halo" with a partition that has own_offset() and one halo chunk (p2p, or the
+        dense table gathered at once); the vertex cut has no table of input rows.
+    Anything else keeps the three nodes and HaloGat / VertexCutGat."""
+    m = plan.get(nd["out"])
+    if m is None or not gat_input_enabled():
+        return False
+    s = ir["sched"]
+    if s.get("gat_mode", 0) != 0 or not s["undirected"] or int(s["kernel_sample"]) != 0:
+        return False
+    weights = {w["name"]: w for w in ir["weights"]}
+    by_out = {n["out"]: n for n in ir["nodes"]}
+    wx = weights[by_out[m["ffn"]]["weight"]]
+    wa, wr = weights[by_out[m["attn"]]["weight"]], weights[nd["weight"]]
+    fin, F, H = int(wx["in"]), int(wx["out"]), int(wa.get("heads", 1))
+    if not (1 <= H <= 8) or F % H or int(wr.get("heads", 1)) != H or wa["in"] != F or wr["in"] != F:
+        return False
+    if F // H not in (4, 8, 16, 32) or not (1 <= fin <= 100) or fin >= F:
+        return False
+    if layout_mode != "halo" or not hasattr(part, "own_offset") or part.chunks != 1:
+        return False
+    return bool(symmetric() if callable(symmetric) else symmetric)
+
+
+def pattern_is_symmetric(g: layout.HostGraph) -> bool:
+    """Whether the square one-segment host graph's CSR equals its transpose's."""
+    if g.n_rows != g.n_cols or g.n_seg != 1:
+        return False
+    t = layout.transpose(g)[0]
+    return bool(np.array_equal(t.rowptr, g.rowptr) and np.array_equal(t.col, g.col))
+
+
+def _gat_in_tmode(n_rows: int) -> bool:
+    """T mode wanted (the backend decides whether it has one): GALA_GAT_IN_T=0 keeps the walk,
+    and T's 3.5 KB per row stays within GALA_GAT_IN_T_MAX_GB (default 64), as in the mirror."""
+    if os.environ.get("GALA_GAT_IN_T", "").startswith("0"):
+        return False
+    return n_rows * 896 * 4 <= float(os.environ.get("GALA_GAT_IN_T_MAX_GB", "64")) * (1 << 30)
+
 
 def check_program(ir: dict, layout_mode: str = "halo") -> None:
     """Raise NotImplementedError when this runtime cannot run the (post-pass) program on the
@@ -263,6 +405,21 @@ class Program:
         self.part, self.agg = self._partition(graph, None)
         own_rowptr = self.part.deg_graph.rowptr if layout_mode == "vcut" else self.part.graph.rowptr
         self._gat = {}
+        # first layers in input space (execution-time fusion of FFN + attention Linears + GAT
+        # [+ ReLU]); the symmetry of the whole pattern is checked once, and only when asked
+        self._in_plan = plan_input_layers(ir)
+        sym = []
+
+        def symmetric():
+            if not sym:
+                sym.append(pattern_is_symmetric(graph))
+            return sym[0]
+        by_out = self._by_out = {nd["out"]: nd for nd in ir["nodes"]}
+        self._in_layers = {v: m for v, m in self._in_plan.items() if input_layer_eligible(
+            ir, by_out[v], self._in_plan, layout_mode, self.part, symmetric)}
+        self._in_skip = {u for m in self._in_layers.values() for u in (m["ffn"], m["attn"], m["relu"]) if u is not None}
+        self.keep_gat_out = False    # --dump: keep the first training forward's GAT layer outputs
+        self.gat_out = {}
         # the aggregation pair (forward, slot 2g+1 backward) of every graph g of the program
         self.aggs = {0: (self.agg, self._partition(layout.transpose(graph)[0], self.part.bounds)[1]
                          if self.directed else self.agg)}
@@ -302,6 +459,11 @@ class Program:
             dist.all_reduce(n_train, group=group)
         self.n_train = float(n_train.item())
         self.invariants = None
+        # the input-space layers, built once per node: each fetches its halo's input rows here
+        for v in self._in_layers:
+            heads = self.modules[by_out[self._in_layers[v]["attn"]]["weight"]].bias.numel()
+            self._gat[v] = gdist.HaloGatInput(self.part, self.X, heads, self.be, self.comm,
+                                              slope=float(by_out[v]["param"]), tmode=_gat_in_tmode(self.part.n))
 
     def _partition(self, g, bounds):
         """(partition, aggregator) of graph g on this rank in the program's layout."""
@@ -329,6 +491,41 @@ class Program:
             self._gat[key] = cls(self.part, F, H, self.be, self.comm, slope=float(nd["param"]))
         return self._gat[key]
 
+    def _gat_input(self, nd, by_out):
+        """An eligible first layer (self._in_layers) through _GatInputLayer; its HaloGatInput
+        was built with the program (the halo's input rows fetched then) and is kept in self._gat.  With
+        gradients off (the eval forward) it is HaloGatInput.forward: prep and the walk, no q
+        exchange and no T."""
+        m = self._in_layers[nd["out"]]
+        ffn, attn, attn_r = (self.modules[w] for w in (by_out[m["ffn"]]["weight"], by_out[m["attn"]]["weight"],
+                                                      nd["weight"]))
+        layer, relu = self._gat[nd["out"]], m["relu"] is not None
+        args = (ffn.weight, ffn.bias, attn.weight, attn.bias, attn_r.weight, attn_r.bias)
+        if not torch.is_grad_enabled():
+            return layer.forward(None, *(t.detach().contiguous() for t in args), relu=relu)
+        return _GatInputLayer.apply(*args, layer, relu)
+
+    def q_exchanges(self) -> int:
+        """q exchanges the input-space layers ran so far on this rank (one per training forward
+        and layer at world > 1; none for a forward without gradients)."""
+        return sum(self._gat[k].q_exchanges for k in self._in_layers if k in self._gat)
+
+    def gat_layers(self):
+        """The summary's `gat_layers`: per GAT node which layer ran and what it moves."""
+        out = []
+        for nd in self.ir["nodes"]:
+            if nd["op"] == "GAT_AGGREGATE" and nd["out"] in self._gat:
+                layer = self._gat[nd["out"]]
+                inp = nd["out"] in self._in_layers
+                if hasattr(layer, "halo_bytes"):
+                    moved = layer.halo_bytes()
+                else:   # VertexCutGat: 2F + 2H floats per sent partial row forward, F backward
+                    moved = layer.part.comm_bytes(3 * layer.F + 2 * layer.H) if self.world > 1 else 0
+                out.append({"node": nd["out"], "kind": "input" if inp else "stats",
+                            "tmode": bool(inp and layer.tmode), "halo_bytes_per_step": int(moved),
+                            "setup_bytes": int(layer.setup_bytes()) if inp else 0})
+        return out
+
     def forward(self):
         if self.samp is not None and self.dynamic:
             ra, rb = (int(v) for v in self._rng.integers(0, 101, 2))
@@ -336,11 +533,23 @@ class Program:
         if self.samp is not None:
             self.samples.append(self.samp[1:])
         vals = {}
+        by_out = self._by_out
         hoisted = self.invariants is None
         for nd in self.ir["nodes"]:
             out = nd["out"]
             if nd.get("hoisted") and not hoisted:
                 vals[out] = self.invariants[out]
+                continue
+            if out in self._in_skip:     # folded into an input-space layer (or already set by it)
+                continue
+            if out in self._in_layers:   # FFN + attention Linears + GAT [+ ReLU] in input space
+                y = self._gat_input(nd, by_out)
+                relu_out = self._in_layers[out]["relu"]
+                vals[out] = y
+                if relu_out is not None:
+                    vals[relu_out] = y
+                if self.keep_gat_out and torch.is_grad_enabled() and out not in self.gat_out:
+                    self.gat_out[out] = y.detach()
                 continue
             op, a = nd["op"], [vals[i] if i >= 0 else None for i in nd["in"]]
             if op == "INPUT":
@@ -386,6 +595,8 @@ class Program:
                     y = _VcutGatFfn.apply(aL.reshape(n, H), x, m.weight, m.bias, layer)
                 else:
                     y = _VcutGat.apply(aL.reshape(n, H), a[1].reshape(n, H), x, layer)
+                if self.keep_gat_out and torch.is_grad_enabled() and out not in self.gat_out:
+                    self.gat_out[out] = y.detach()
             elif op == "FFN":
                 y = self.modules[nd["weight"]](a[0])
             elif op == "RELU":
@@ -439,6 +650,15 @@ def main(argv=None):
                     help="run the collectives even on one rank (RCCL at world 1 on one GPU)")
     ap.add_argument("--exchange", default="auto", choices=["auto", "dense", "sparse"],
                     help="vcut: dense reduce-scatter, sparse DCSR all-to-all, or auto (touched fraction)")
+    ap.add_argument("--eval", action="store_true",
+                    help="the program's eval forward (torch.no_grad()) before the first and after the last epoch; "
+                         "the summary's `eval` counts its forwards and messages, the dump keeps the first one's "
+                         "predictions (eval_prediction)")
+    ap.epilog = ("GAT programs: a first layer (FFN of the input features, its attention Linears, the aggregation) "
+                 "within the gala_gat_in_* kernels' limits runs in input space on the halo layout -- the halo's "
+                 "input rows are fetched once, 4 H bytes of q per halo row move per step, eval forwards move "
+                 "nothing; GALA_GAT_INPUT=0 keeps the three ops (HaloGat).  The summary's gat_layers names the "
+                 "layer every GAT node ran.")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -514,6 +734,24 @@ def main(argv=None):
     iters = args.iters if args.iters is not None else max(int(s.get("iterations", 0)), 1)
     sync = torch.cuda.synchronize if dev.type == "cuda" else (lambda: None)
     fwd_t, ep_t, losses = [], [], []
+    prog.keep_gat_out = bool(args.dump)
+    from .comm import message_stats
+    ev = {"forwards": 0, "q_exchanges": 0, "messages": {}}
+
+    def eval_forward():
+        """The program's eval forward: no gradients, so an input-space layer runs no exchange."""
+        calls = {k: v["calls"] for k, v in message_stats().items() if isinstance(v, dict)}
+        q0 = prog.q_exchanges()
+        with torch.no_grad():
+            out = prog.forward()
+        sync()
+        for k, v in message_stats().items():
+            if isinstance(v, dict) and v["calls"] > calls.get(k, 0):
+                ev["messages"][k] = ev["messages"].get(k, 0) + v["calls"] - calls.get(k, 0)
+        ev["forwards"] += 1
+        ev["q_exchanges"] += prog.q_exchanges() - q0
+        return out
+    eval_pred = eval_forward() if args.eval else None
     for epoch in range(iters):
         sync()
         t0 = time.perf_counter()
@@ -530,6 +768,8 @@ def main(argv=None):
         opt.step()
         sync()
         t2 = time.perf_counter()
+        if epoch == 0 and args.dump:   # the weights after the first Adam step (the dump's step1:<name>)
+            step1 = {k: v.detach().cpu().numpy() for k, v in prog.modules.named_parameters()}
         lt = loss.detach().reshape(1).to(torch.float64)
         if distributed:
             lt = lt.to(dev) if prog.comm.rccl else lt.cpu()
@@ -540,27 +780,35 @@ def main(argv=None):
         fwd_t.append(t1 - t0)
         ep_t.append(t2 - t0)
     keep = slice(min(4, iters - 1), None)  # the reference drops its first epochs (gala.cu:613-637)
+    if args.eval:
+        eval_forward()
     if args.dump:
         sizes = [int(bounds[q + 1] - bounds[q]) for q in range(world)]
-        pr = first_pred
-        if world > 1:   # equal-sized blocks for all_gather: pad every rank's rows
-            gdev = dev if prog.comm.rccl else torch.device("cpu")
-            pad = torch.full((max(sizes), pr.shape[1]), float("nan"), device=gdev)
-            pad[:pr.shape[0]] = pr.to(gdev)
-            parts = [torch.empty_like(pad) for _ in sizes]
-            dist.all_gather(parts, pad)
-            pr = torch.cat([t[:n] for t, n in zip(parts, sizes)])
-        pr = pr.cpu()
+
+        def all_rows(pr):
+            """Every rank's rows of a row-partitioned value, in vertex order, on the host."""
+            if world > 1:   # equal-sized blocks for all_gather: pad every rank's rows
+                gdev = dev if prog.comm.rccl else torch.device("cpu")
+                pad = torch.full((max(sizes), pr.shape[1]), float("nan"), device=gdev)
+                pad[:pr.shape[0]] = pr.to(gdev)
+                parts = [torch.empty_like(pad) for _ in sizes]
+                dist.all_gather(parts, pad)
+                pr = torch.cat([t[:n] for t, n in zip(parts, sizes)])
+            return pr.cpu().numpy()
+        pr = all_rows(first_pred)
+        # the first training forward's GAT layer outputs (gat_out:<node>), the first eval forward
+        more = {f"gat_out:{k}": all_rows(v) for k, v in sorted(prog.gat_out.items())}
+        if eval_pred is not None:
+            more["eval_prediction"] = all_rows(eval_pred)
         if rank == 0:
             rows_d = np.arange(0, g.n_rows, max(args.dump_stride, 1))
-            np.savez(args.dump, prediction=pr.numpy()[rows_d], rows=rows_d, losses=np.array(losses),
+            np.savez(args.dump, prediction=pr[rows_d], rows=rows_d, losses=np.array(losses),
                      rowptr=g_in.rowptr, col=g_in.col, weights=np.array(json.dumps(init_weights)),
                      samples=np.array(prog.samples, np.int64).reshape(-1, 2),
-                     **{"grad:" + k: v for k, v in first_grads.items()})
+                     **{"grad:" + k: v for k, v in first_grads.items()},
+                     **{"step1:" + k: v for k, v in step1.items()}, **{k: v[rows_d] for k, v in more.items()})
     messages = None
     if distributed:   # every rank: the maxima over ranks are collectives
-        from .comm import message_stats
-
         def reduce_max(x):
             t = torch.tensor([x], dtype=torch.float64, device=dev if prog.comm.rccl else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -572,6 +820,9 @@ def main(argv=None):
                           "vertices": g.n_rows, "edges": g.nnz, "layout": args.layout,
                           "halo": prog.part.halo_mode if args.layout == "halo" else None,
                           "exchange": prog.part.exchange if args.layout == "vcut" else None,
+                          "gat_layers": prog.gat_layers(), "q_exchanges": prog.q_exchanges(),
+                          "eval": ev if args.eval else None,
+                          "epoch_median_s": float(np.median(ep_t[keep])), "epoch_s": [float(t) for t in ep_t],
                           "fwd_mean_s": float(np.mean(fwd_t[keep])), "epoch_mean_s": float(np.mean(ep_t[keep])),
                           "loss_first": losses[0], "loss_last": losses[-1]}), flush=True)
         print(f"{np.mean(fwd_t[keep]):.6g},{np.mean(ep_t[keep]):.6g}", flush=True)
