@@ -1038,6 +1038,265 @@ extern "C" int gala_cpu_gat_bwd_stats_linear_f32(const gala_csr_t *A, const floa
     return GALA_OK;
 }
 
+// ---- the exact pair (gala_hip.h, gala_gat_{fwd,bwd}_stats_exact_f32) ---------------------
+namespace {
+
+// The kernels' row layout: vectors of `vec` floats, `hw` lanes per head, `ch` vectors per lane.
+struct ExactShape {
+    int vec, hw, ch;
+};
+
+// vec from the row strides as the kernels pick it (the pointers are taken as aligned)
+int exact_shape(int32_t F, int32_t H, std::initializer_list<int64_t> lds, ExactShape *sh) {
+    const int D = F / H;
+    int vec = 4;
+    auto ok = [&](int v) {
+        bool padded = H == 1, mult = true;
+        for (int64_t ld : lds) {
+            padded = padded && ld >= (F + v - 1) / v * v;
+            mult = mult && ld % v == 0;
+        }
+        return (D % v == 0 || padded) && mult;
+    };
+    while (vec > 1 && !ok(vec)) vec >>= 1;
+    const int L = (F + vec - 1) / vec;
+    if (L > 64) return GALA_ERR_UNSUPPORTED;
+    const int ch = (H == 1 && vec < 4 && L > 16) ? (L + 15) / 16 : 1;
+    int G = 16;
+    if (ch == 1) {
+        G = 1;
+        while (G < L) G <<= 1;
+    }
+    const int hw = (D % vec == 0) ? D / vec : 0;
+    if (H > 1 && (hw == 0 || (hw & (hw - 1)))) return GALA_ERR_UNSUPPORTED;
+    sh->vec = vec, sh->ch = ch, sh->hw = H == 1 ? G : hw;
+    return GALA_OK;
+}
+
+// <a, b> over one head's n elements: lane l's fma chain over its vectors, then the xor butterfly
+float exact_lane_dot(const float *a, const float *b, int n, const ExactShape &sh) {
+    float v[64];
+    for (int l = 0; l < sh.hw; ++l) {
+        float s = 0.0f;
+        for (int c = 0; c < sh.ch; ++c)
+            for (int i = 0; i < sh.vec; ++i) {
+                const int f = (c * sh.hw + l) * sh.vec + i;
+                if (f < n) s = fmaf(a[f], b[f], s);
+            }
+        v[l] = s;
+    }
+    for (int o = sh.hw / 2; o >= 1; o /= 2) {
+        float w[64];
+        for (int l = 0; l < sh.hw; ++l) w[l] = v[l] + v[l ^ o];
+        for (int l = 0; l < sh.hw; ++l) v[l] = w[l];
+    }
+    return v[0];
+}
+
+// f(e0, e1) over the pieces of row r whose sums the kernels keep apart: the 512-edge
+// chunks of a hub row of A's plan, else the row's segments
+template <typename Fn>
+void exact_row_pieces(const gala_csr_t *A, int64_t r, Fn &&f) {
+    const gala_split_plan_t *plan = A->split;
+    if (plan && plan->n_rows_split > 0 && plan->n_chunks > 0 && A->n_seg == 1 && plan->chunk >= 1 &&
+        plan->threshold >= 1 && A->rowptr[r + 1] - A->rowptr[r] > plan->threshold) {
+        for (int64_t c0 = A->rowptr[r]; c0 < A->rowptr[r + 1]; c0 += plan->chunk)
+            f(c0, std::min<int64_t>(c0 + plan->chunk, A->rowptr[r + 1]));
+        return;
+    }
+    for (int32_t s = 0; s < A->n_seg; ++s) {
+        int64_t e0, e1;
+        row_range(A, s, r, e0, e1);
+        f(e0, e1);
+    }
+}
+
+constexpr int kExactU = 8;  // edges per batch (one max rescale each)
+
+}  // namespace
+
+extern "C" int gala_cpu_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR,
+                                                const float *wR, const float *bR, const float *X, int64_t ldx,
+                                                int32_t F, int32_t heads, float slope, float *Y, int64_t ldy,
+                                                float *lse, float *Ym, int64_t ldym, float *sma, float *aR_out,
+                                                void *) {
+    int st = check_csr(A);
+    if (st) return st;
+    if (heads < 1 || F < 1 || F % heads != 0 || ldx < F || ldy < F || ldym < F) return GALA_ERR_INVALID_ARG;
+    if (A->n_rows == 0) return GALA_OK;
+    if (!aL || (!aR && !wR) || !Y || !lse || !Ym || !sma || !X) return GALA_ERR_INVALID_ARG;
+    if (A->n_cols != A->n_rows || (aR_out && aR)) return GALA_ERR_INVALID_ARG;
+    ExactShape sh;
+    if ((st = exact_shape(F, heads, {ldx, ldy, ldym}, &sh))) return st;
+    const int32_t H = heads, D = F / H;
+    std::vector<float> rc;
+    if (!aR) {
+        rc.resize((size_t)A->n_cols * H);
+#pragma omp parallel for schedule(static, 4096)
+        for (int64_t j = 0; j < A->n_cols; ++j)
+            for (int32_t h = 0; h < H; ++h)
+                rc[(size_t)j * H + h] = exact_lane_dot(wR + h * D, X + j * ldx + h * D, D, sh) + (bR ? bR[h] : 0.0f);
+        aR = rc.data();
+        if (aR_out) std::copy(rc.begin(), rc.end(), aR_out);
+    }
+#pragma omp parallel
+    {
+        std::vector<float> acc((size_t)D), accm((size_t)D), pa((size_t)D), pam((size_t)D);
+#pragma omp for schedule(dynamic, kRowChunk)
+        for (int64_t r = 0; r < A->n_rows; ++r)
+            for (int32_t h = 0; h < H; ++h) {
+                const float al = aL[r * H + h];
+                // one piece's edges into the state (a, am, m, sum, sm)
+                auto range = [&](int64_t e0, int64_t e1, float *a, float *am, float &m, float &sum, float &sm) {
+                    for (int64_t j0 = e0; j0 < e1; j0 += kExactU) {
+                        const int64_t j1 = std::min<int64_t>(j0 + kExactU, e1);
+                        float z[kExactU], mb = -INFINITY;
+                        bool pos[kExactU];
+                        for (int64_t e = j0; e < j1; ++e) {
+                            const float t = al + aR[(int64_t)A->col[e] * H + h];
+                            pos[e - j0] = t > 0.0f;
+                            z[e - j0] = pos[e - j0] ? t : t * slope;
+                            mb = fmaxf(mb, z[e - j0]);
+                        }
+                        if (mb > m) {
+                            const float s = (m == -INFINITY) ? 0.0f : expf(m - mb);
+                            sum = sum * s;
+                            sm = sm * s;
+                            for (int32_t f = 0; f < D; ++f) a[f] = a[f] * s, am[f] = am[f] * s;
+                            m = mb;
+                        }
+                        for (int64_t e = j0; e < j1; ++e) {
+                            const float pe = expf(z[e - j0] - m);
+                            const float mp = pos[e - j0] ? pe : pe * slope;
+                            sum = sum + pe;
+                            sm = sm + mp;
+                            const float *xr = X + (int64_t)A->col[e] * ldx + h * D;
+                            for (int32_t f = 0; f < D; ++f) {
+                                a[f] = fmaf(pe, xr[f], a[f]);
+                                am[f] = fmaf(mp, xr[f], am[f]);
+                            }
+                        }
+                    }
+                };
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                std::fill(accm.begin(), accm.end(), 0.0f);
+                float m = -INFINITY, sum = 0.0f, sm = 0.0f;
+                const gala_split_plan_t *plan = A->split;
+                const bool hub = plan && plan->n_rows_split > 0 && plan->n_chunks > 0 && A->n_seg == 1 &&
+                                 plan->chunk >= 1 && plan->threshold >= 1 &&
+                                 A->rowptr[r + 1] - A->rowptr[r] > plan->threshold;
+                exact_row_pieces(A, r, [&](int64_t e0, int64_t e1) {
+                    if (!hub) {
+                        range(e0, e1, acc.data(), accm.data(), m, sum, sm);
+                        return;
+                    }
+                    // a chunk's partial from an empty state, then the fix-up's rescaled combine
+                    std::fill(pa.begin(), pa.end(), 0.0f);
+                    std::fill(pam.begin(), pam.end(), 0.0f);
+                    float mc = -INFINITY, sc = 0.0f, smc = 0.0f;
+                    range(e0, e1, pa.data(), pam.data(), mc, sc, smc);
+                    if (mc == -INFINITY) return;
+                    const float mn = fmaxf(m, mc);
+                    const float a = (m == -INFINITY) ? 0.0f : expf(m - mn);
+                    const float b = expf(mc - mn);
+                    m = mn;
+                    sum = fmaf(sum, a, sc * b);
+                    sm = fmaf(sm, a, smc * b);
+                    for (int32_t f = 0; f < D; ++f) {
+                        acc[f] = fmaf(acc[f], a, pa[f] * b);
+                        accm[f] = fmaf(accm[f], a, pam[f] * b);
+                    }
+                });
+                const bool empty = sum == 0.0f;
+                const float q = empty ? 0.0f : 1.0f / sum;
+                for (int32_t f = 0; f < D; ++f) {
+                    Y[r * ldy + h * D + f] = acc[f] * q;
+                    Ym[r * ldym + h * D + f] = accm[f] * q;
+                }
+                sma[r * H + h] = sm * q;
+                lse[r * H + h] = empty ? 0.0f : m + logf(sum);
+            }
+    }
+    return GALA_OK;
+}
+
+extern "C" int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR,
+                                                const float *X, int64_t ldx, const float *dY, int64_t lddy,
+                                                int32_t F, int32_t heads, float slope, const float *lse,
+                                                const float *Y, int64_t ldy, const float *Ym, int64_t ldym,
+                                                const float *sma, float *side, float *dX, int64_t lddx,
+                                                float *d_aL, float *d_aR, void *) {
+    int st = check_csr(A);
+    if (st) return st;
+    if (heads < 1 || F < 1 || F % heads != 0 || ldx < F || lddy < F || ldy < F || ldym < F || lddx < F)
+        return GALA_ERR_INVALID_ARG;
+    if (A->n_rows == 0) return GALA_OK;
+    if (!aL || !aR || !X || !dY || !lse || !Y || !Ym || !sma || !side || !dX || !d_aL || !d_aR)
+        return GALA_ERR_INVALID_ARG;
+    if (A->n_cols != A->n_rows) return GALA_ERR_INVALID_ARG;
+    ExactShape sh;
+    if ((st = exact_shape(F, heads, {ldx, lddy, ldy, ldym, lddx}, &sh))) return st;
+    const int32_t H = heads, D = F / H;
+    // the row-local pre-pass: g, d_aL and the side lines {aL, lse, g, 0}
+#pragma omp parallel for schedule(static, 1024)
+    for (int64_t r = 0; r < A->n_rows; ++r)
+        for (int32_t h = 0; h < H; ++h) {
+            const int64_t o = r * H + h;
+            const float g = exact_lane_dot(dY + r * lddy + h * D, Y + r * ldy + h * D, D, sh);
+            const float s1 = exact_lane_dot(dY + r * lddy + h * D, Ym + r * ldym + h * D, D, sh);
+            d_aL[o] = s1 - g * sma[o];
+            side[o * 4 + 0] = aL[o], side[o * 4 + 1] = lse[o], side[o * 4 + 2] = g, side[o * 4 + 3] = 0.0f;
+        }
+    // the gather pass: row c over its neighbours r
+#pragma omp parallel
+    {
+        std::vector<float> dx((size_t)D), dxm((size_t)D), pa((size_t)D), pam((size_t)D);
+#pragma omp for schedule(dynamic, kRowChunk)
+        for (int64_t c = 0; c < A->n_rows; ++c)
+            for (int32_t h = 0; h < H; ++h) {
+                const float ar = aR[c * H + h];
+                auto range = [&](int64_t e0, int64_t e1, float *a, float *am, float &sg) {
+                    for (int64_t e = e0; e < e1; ++e) {
+                        const int64_t r = A->col[e];
+                        const float *sd = side + (r * H + h) * 4;
+                        const float t = sd[0] + ar;
+                        const bool pos = t > 0.0f;
+                        const float al = expf((pos ? t : t * slope) - sd[1]);
+                        const float ma = pos ? al : al * slope;
+                        sg = sg + ma * sd[2];
+                        const float *yr = dY + r * lddy + h * D;
+                        for (int32_t f = 0; f < D; ++f) {
+                            a[f] = fmaf(al, yr[f], a[f]);
+                            am[f] = fmaf(ma, yr[f], am[f]);
+                        }
+                    }
+                };
+                std::fill(dx.begin(), dx.end(), 0.0f);
+                std::fill(dxm.begin(), dxm.end(), 0.0f);
+                float sg = 0.0f;
+                const gala_split_plan_t *plan = A->split;
+                const bool hub = plan && plan->n_rows_split > 0 && plan->n_chunks > 0 && A->n_seg == 1 &&
+                                 plan->chunk >= 1 && plan->threshold >= 1 &&
+                                 A->rowptr[c + 1] - A->rowptr[c] > plan->threshold;
+                exact_row_pieces(A, c, [&](int64_t e0, int64_t e1) {
+                    if (!hub) {
+                        range(e0, e1, dx.data(), dxm.data(), sg);
+                        return;
+                    }
+                    std::fill(pa.begin(), pa.end(), 0.0f);
+                    std::fill(pam.begin(), pam.end(), 0.0f);
+                    float sgc = 0.0f;
+                    range(e0, e1, pa.data(), pam.data(), sgc);
+                    sg = sg + sgc;
+                    for (int32_t f = 0; f < D; ++f) dx[f] = dx[f] + pa[f], dxm[f] = dxm[f] + pam[f];
+                });
+                for (int32_t f = 0; f < D; ++f) dX[c * lddx + h * D + f] = dx[f];
+                d_aR[c * H + h] = exact_lane_dot(dxm.data(), X + c * ldx + h * D, D, sh) - sg;
+            }
+    }
+    return GALA_OK;
+}
+
 extern "C" int gala_cpu_head_attn_f32(int64_t n_rows, int32_t F, int32_t heads, const float *X, int64_t ldx,
                                       const float *w, const float *b, float *out, void *) {
     if (n_rows < 0 || F < 1 || heads < 1 || F % heads != 0 || ldx < F) return GALA_ERR_INVALID_ARG;

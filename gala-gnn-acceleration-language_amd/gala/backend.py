@@ -78,6 +78,16 @@ class HipBackend:
         """(dX, d_aL) of the REF layer from its row statistics (gala_gat_bwd_stats_f32)."""
         return self.ops.gat_bwd_stats(g, aL, aR, dY, q, Y, Ym, sma, heads=heads, slope=slope)
 
+    def gat_stats_exact(self, g, aL, aR, X, heads, slope, wR=None, bR=None):
+        """(Y, lse, Ym, sma, aR) of the stable-softmax layer (gala_gat_fwd_stats_exact_f32)."""
+        return self.ops.gat_fwd_stats_exact(g, aL, X, aR=aR, wR=wR, bR=bR, heads=heads, slope=slope)
+
+    def gat_bwd_stats_exact(self, g, aL, aR, X, dY, lse, Y, Ym, sma, heads, slope, symmetric=None):
+        """(dX, d_aL, d_aR), the layer's true gradients on a symmetric pattern
+        (gala_gat_bwd_stats_exact_f32)."""
+        return self.ops.gat_bwd_stats_exact(g, aL, aR, X, dY, lse, Y, Ym, sma, heads=heads, slope=slope,
+                                            symmetric=symmetric)
+
     def head_attn(self, X, w, b, heads):
         """[n, heads] per-head attention logits <X[:, head h], w_h> + b_h (gala_head_attn_f32)."""
         return self.ops.head_attn(X, w, b, heads=heads)
@@ -177,6 +187,29 @@ class CpuGraph:
     def csr(self):
         return ctypes.byref(self.c)
 
+    def set_split_plan(self, threshold: int, chunk: int = 512):
+        """Rows longer than `threshold` become hub rows summed as `chunk`-edge partials, the
+        association of the HIP kernels' hub-row plan (the host twins read no workspace)."""
+        deg = np.diff(self.rowptr[: self.n_rows + 1]) if self.hg.n_seg == 1 else np.zeros(0, np.int64)
+        hubs = deg[deg > threshold]
+        plan = _abi.gala_split_plan_t()
+        plan.threshold, plan.chunk = max(int(threshold), 1), int(chunk)
+        plan.n_rows_split, plan.n_chunks = int(hubs.size), int(((hubs + chunk - 1) // chunk).sum())
+        self._plan = plan
+        self.c.split = ctypes.addressof(plan) if hubs.size else None
+
+    @property
+    def symmetric(self) -> bool:
+        """Whether the square one-segment pattern equals its transpose (tested once)."""
+        if getattr(self, "_symmetric", None) is None:
+            from . import layout
+            hg = self.hg
+            self._symmetric = False
+            if hg.n_rows == hg.n_cols and hg.n_seg == 1:
+                t = layout.transpose(hg)[0]
+                self._symmetric = bool(np.array_equal(t.rowptr, hg.rowptr) and np.array_equal(t.col, hg.col))
+        return self._symmetric
+
 
 def _hp(t: torch.Tensor):
     if t is None:
@@ -275,6 +308,26 @@ class CpuBackend:
                       _hp(dY_rows), F, heads, slope, _hp(q), _hp(Y), Y.stride(0), _hp(Ym), Ym.stride(0), _hp(sma),
                       _hp(dX), dX.stride(0), _hp(d_aL), None)
         return dX, d_aL
+
+    def gat_stats_exact(self, g: CpuGraph, aL, aR, X, heads, slope, wR=None, bR=None):
+        n, F = g.n_rows, X.shape[1]
+        Y, Ym = torch.empty((n, F)), torch.empty((n, F))
+        lse, sma = torch.empty(n * heads), torch.empty(n * heads)
+        aR_out = torch.empty(n * heads) if aR is None else None
+        _abi.call_cpu("gala_gat_fwd_stats_exact_f32", g.csr(), _hp(aL), _hp(aR), _hp(wR), _hp(bR), _hp(X),
+                      X.stride(0), F, heads, slope, _hp(Y), F, _hp(lse), _hp(Ym), F, _hp(sma), _hp(aR_out), None)
+        return Y, lse, Ym, sma, (aR if aR is not None else aR_out)
+
+    def gat_bwd_stats_exact(self, g: CpuGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads, slope, symmetric=None):
+        if not (g.symmetric if symmetric is None else symmetric):
+            raise ValueError("gat_bwd_stats_exact: the pattern is not symmetric")
+        n, F = g.n_rows, dY.shape[1]
+        dX = torch.empty((n, F), dtype=torch.float32)
+        d_aL, d_aR, side = torch.empty(n * heads), torch.empty(n * heads), torch.empty(n * heads * 4)
+        _abi.call_cpu("gala_gat_bwd_stats_exact_f32", g.csr(), _hp(aL), _hp(aR), _hp(X), X.stride(0), _hp(dY),
+                      dY.stride(0), F, heads, slope, _hp(lse), _hp(Y), Y.stride(0), _hp(Ym), Ym.stride(0), _hp(sma),
+                      _hp(side), _hp(dX), dX.stride(0), _hp(d_aL), _hp(d_aR), None)
+        return dX, d_aL, d_aR
 
     def head_attn(self, X, w, b, heads):
         out = torch.empty((X.shape[0], heads), dtype=torch.float32)

@@ -492,6 +492,42 @@ def gat_bwd_stats(g: DeviceGraph, aL, aR, dY, q, Y, Ym, sma, heads=1, slope=0.2,
     return dX, d_aL
 
 
+def gat_fwd_stats_exact(g: DeviceGraph, aL, X, aR=None, wR=None, bR=None, heads=1, slope=0.2):
+    """gala_gat_fwd_stats_exact_f32 (the stable softmax, square pattern): returns (Y, lse, Ym, sma, aR)
+    with lse[r, h] the log-sum-exp of the row's LeakyReLU'd logits and aR the source logits the
+    backward must read (the given aR, or the kernel's recompute from wR, bR)."""
+    F = X.shape[1]
+    Y, Ym = _rows_like(X, g.n_rows), _rows_like(X, g.n_rows)
+    lse = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32)
+    sma = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32)
+    aR_out = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32) if aR is None else None
+    _abi.call("gala_gat_fwd_stats_exact_f32", g.csr(2 * ((F + 3) // 4 * 4) + 3 * heads), _dp(aL), _dp(aR), _dp(wR),
+              _dp(bR), _dp(X), X.stride(0), F, heads, slope, _dp(Y), Y.stride(0), _dp(lse), _dp(Ym), Ym.stride(0),
+              _dp(sma), _dp(aR_out), _stream())
+    return Y, lse, Ym, sma, (aR if aR is not None else aR_out)
+
+
+def gat_bwd_stats_exact(g: DeviceGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads=1, slope=0.2, symmetric=None):
+    """gala_gat_bwd_stats_exact_f32: the layer's true gradients (dX, d_aL, d_aR) from the forward's
+    row statistics; aR as gat_fwd_stats_exact returned it.  The regrouping holds on a symmetric
+    pattern only: symmetric=None tests g once (pattern_is_symmetric, kept on g), True is the
+    caller's assertion; anything else raises ValueError before a launch."""
+    if symmetric is None:
+        symmetric = pattern_is_symmetric(g)
+    if not symmetric:
+        raise ValueError("gat_bwd_stats_exact: the pattern is not symmetric (row c's neighbours must be its "
+                         "in-edges); take gat_fwd_ex / gat_bwd_ex in GALA_SOFTMAX_FIXED mode")
+    F = dY.shape[1]
+    dX = _rows_like(dY, g.n_rows)
+    d_aL = torch.empty(g.n_rows * heads, device=dY.device, dtype=torch.float32)
+    d_aR = torch.empty(g.n_rows * heads, device=dY.device, dtype=torch.float32)
+    side = torch.empty(g.n_rows * heads * 4, device=dY.device, dtype=torch.float32)
+    _abi.call("gala_gat_bwd_stats_exact_f32", g.csr(2 * ((F + 3) // 4 * 4) + heads), _dp(aL), _dp(aR), _dp(X),
+              X.stride(0), _dp(dY), dY.stride(0), F, heads, slope, _dp(lse), _dp(Y), Y.stride(0), _dp(Ym),
+              Ym.stride(0), _dp(sma), _dp(side), _dp(dX), dX.stride(0), _dp(d_aL), _dp(d_aR), _stream())
+    return dX, d_aL, d_aR
+
+
 def head_attn(X, w, b=None, heads=1):
     """gala_head_attn_f32: out[r, h] = <X[r, head h], w[head h]> + b[h] ([N, heads])."""
     N, F = X.shape

@@ -42,6 +42,8 @@ struct Backend {
     decltype(&gala_gat_fwd_stats_f32) gat_fwd_stats;
     decltype(&gala_gat_bwd_stats_f32) gat_bwd_stats;
     decltype(&gala_gat_bwd_stats_linear_f32) gat_bwd_stats_linear;
+    decltype(&gala_gat_fwd_stats_exact_f32) gat_fwd_stats_exact;
+    decltype(&gala_gat_bwd_stats_exact_f32) gat_bwd_stats_exact;
     decltype(&gala_head_attn_f32) head_attn;
     decltype(&gala_head_attn_bwd_f32) head_attn_bwd;
     decltype(&gala_edge_permute_f32) permute;
@@ -62,6 +64,7 @@ const Backend kHip{gala_spmm_ex_f32, gala_degree_f32, gala_row_broadcast_f32,
                    gala_gat_bwd_f32, gala_gat_fwd_attn_f32, gala_gat_bwd_attn_f32,
                    gala_gat_fwd_ex_f32, gala_gat_bwd_ex_f32, gala_gat_bwd_fused_f32,
                    gala_gat_fwd_stats_f32, gala_gat_bwd_stats_f32, gala_gat_bwd_stats_linear_f32,
+                   gala_gat_fwd_stats_exact_f32, gala_gat_bwd_stats_exact_f32,
                    gala_head_attn_f32, gala_head_attn_bwd_f32,
                    gala_edge_permute_f32, gala_dense_grad_workspace, gala_dense_grad_f32,
                    gala_gat_in_prep_f32, gala_gat_in_fwd_f32, gala_gat_in_bwd_workspace, gala_gat_in_bwd_f32,
@@ -74,6 +77,7 @@ const Backend kCpu{gala_cpu_spmm_ex_f32, gala_cpu_degree_f32, gala_cpu_row_broad
                    gala_cpu_gat_fwd_attn_f32, gala_cpu_gat_bwd_attn_f32,
                    gala_cpu_gat_fwd_ex_f32, gala_cpu_gat_bwd_ex_f32, gala_cpu_gat_bwd_fused_f32,
                    gala_cpu_gat_fwd_stats_f32, gala_cpu_gat_bwd_stats_f32, gala_cpu_gat_bwd_stats_linear_f32,
+                   gala_cpu_gat_fwd_stats_exact_f32, gala_cpu_gat_bwd_stats_exact_f32,
                    gala_cpu_head_attn_f32, gala_cpu_head_attn_bwd_f32,
                    gala_cpu_edge_permute_f32, gala_cpu_dense_grad_workspace,
                    gala_cpu_dense_grad_f32, gala_cpu_gat_in_prep_f32, gala_cpu_gat_in_fwd_f32,
@@ -471,6 +475,7 @@ int GraphSlots::push(torch::Tensor offsets, torch::Tensor cols, torch::Tensor va
         mg = make_merged_csr(offsets, cols, bounds.back(), segs);
     merged.push_back(mg);
     pattern_t.push_back(nullptr);
+    holds_previous.push_back(-1);
     if (offset_graph.size() == 1) nrows = offsets.numel() / segs - 1;
     return (int)offset_graph.size() - 1;
 }
@@ -1037,6 +1042,88 @@ bool gat_backward_stats(const torch::Tensor &l, const GatStats &o, const torch::
     return true;
 }
 
+// The exact pair for a FIXED layer (gala_gat_{fwd,bwd}_stats_exact_f32): the stable softmax
+// and the true gradients from row statistics -- no alpha, no permutation, one gather of dY
+// rows.  Taken when the forward pattern is one square segment that is symmetric (a host
+// transpose on first use, kept with the pattern) and slot 2li+1 holds that same pattern (the
+// runtime uploads the transpose there: compared once per pair of slots).
+// GALA_GAT_EXACT_STATS=0 keeps the alpha-storing path.
+}  // namespace
+const PatternT &transposed_pattern(int64_t idx);
+namespace {
+bool exact_stats_enabled() {  // read per layer call: an A/B run switches it inside one process
+    const char *e = std::getenv("GALA_GAT_EXACT_STATS");
+    return !(e && e[0] == '0');
+}
+
+bool exact_stats_layer(int64_t li, int64_t x_rows) {
+    if (!exact_stats_enabled()) return false;
+    Slot fw = slot(2 * li), bw = slot(2 * li + 1);
+    if (fw.segs != 1 || bw.segs != 1 || fw.off.numel() - 1 != x_rows) return false;
+    // slot 2li+1 must hold the forward's pattern: the same tensors, or equal ones (compared on
+    // the device once per slot).  A directed graph's transpose differs from it, so such a layer
+    // leaves here without the host transpose below
+    if (!same_pattern(fw, bw)) {
+        int8_t &same = global_slots().holds_previous[2 * li + 1];
+        if (same < 0)
+            same = bw.off.numel() == fw.off.numel() && bw.cols.numel() == fw.cols.numel() &&
+                   torch::equal(bw.off, fw.off) && torch::equal(bw.cols, fw.cols);
+        if (!same) return false;
+    }
+    return transposed_pattern(2 * li).symmetric;  // tested once, kept with the slot
+}
+
+struct GatExact {
+    torch::Tensor Y, lse, Ym, sma, aR;  // aR: the given logits, or the kernel's recompute
+};
+
+// One launch of gala_gat_fwd_stats_exact_f32 on slot 2li; false when the kernel does not
+// take this shape (the caller keeps the alpha-storing path).
+bool gat_forward_exact(const Slot &s, const torch::Tensor &l, const torch::Tensor &r, const torch::Tensor &x,
+                       const torch::Tensor &wR, const torch::Tensor &bR, int heads, double slope, GatExact &o) {
+    CsrView cv = view(s.off, s.cols, nullptr, s.bounds, s.segs);
+    const int64_t nrows = cv.c.n_rows, F = x.size(1);
+    cv.c.n_cols = x.size(0);
+    with_workspace(cv, s.off, 2 * ((F + 3) / 4 * 4) + 3 * heads);  // hub rows: {acc, m, sum, accm, sma}
+    auto Y = rows_like(x, nrows), Ym = rows_like(x, nrows);
+    auto lse = torch::empty({nrows * heads}, fopts(x)), sma = torch::empty({nrows * heads}, fopts(x));
+    torch::Tensor aR = r.defined() ? r : torch::empty({nrows * heads}, fopts(x));
+    const int st = be(s.off).gat_fwd_stats_exact(
+        &cv.c, l.data_ptr<float>(), r.defined() ? r.data_ptr<float>() : nullptr,
+        r.defined() ? nullptr : wR.data_ptr<float>(), (!r.defined() && bR.defined()) ? bR.data_ptr<float>() : nullptr,
+        x.data_ptr<float>(), x.stride(0), (int32_t)F, heads, (float)slope, Y.data_ptr<float>(), Y.stride(0),
+        lse.data_ptr<float>(), Ym.data_ptr<float>(), Ym.stride(0), sma.data_ptr<float>(),
+        r.defined() ? nullptr : aR.data_ptr<float>(), stream_of(s.off));
+    if (st == GALA_ERR_UNSUPPORTED) return false;
+    check(st, "gala_gat_fwd_stats_exact_f32");
+    o = {Y, lse, Ym, sma, aR};
+    return true;
+}
+
+// The exact backward: dX, d_aL and d_aR (distinct) from the forward's rows.
+bool gat_backward_exact(const torch::Tensor &l, const GatExact &o, const torch::Tensor &x,
+                        const torch::Tensor &dY_in, int64_t li, double slope, int heads, GatGrads &g) {
+    Slot fw = slot(2 * li);
+    const torch::Tensor dY = heads == 1 ? pad_rows4(dY_in) : dY_in.contiguous();
+    const int64_t F = o.Y.size(1), nrows = fw.off.numel() / fw.segs - 1;
+    CsrView cf = view(fw.off, fw.cols, nullptr, fw.bounds, fw.segs);
+    cf.c.n_cols = dY.size(0);
+    with_workspace(cf, fw.off, 2 * ((F + 3) / 4 * 4) + heads);  // hub rows: {dX, dXm, sg}
+    check_on(dY, fw.off, "grad");
+    auto dX = rows_like(dY, nrows);
+    auto daL = torch::empty_like(l), daR = torch::empty_like(l);
+    auto side = torch::empty({nrows * heads * 4}, fopts(x));   // {aL, lse, g, 0} per (row, head)
+    const int st = be(fw.off).gat_bwd_stats_exact(
+        &cf.c, l.data_ptr<float>(), o.aR.data_ptr<float>(), x.data_ptr<float>(), x.stride(0), dY.data_ptr<float>(),
+        dY.stride(0), (int32_t)F, heads, (float)slope, o.lse.data_ptr<float>(), o.Y.data_ptr<float>(), o.Y.stride(0),
+        o.Ym.data_ptr<float>(), o.Ym.stride(0), o.sma.data_ptr<float>(), side.data_ptr<float>(),
+        dX.data_ptr<float>(), dX.stride(0), daL.data_ptr<float>(), daR.data_ptr<float>(), stream_of(fw.off));
+    if (st == GALA_ERR_UNSUPPORTED) return false;
+    check(st, "gala_gat_bwd_stats_exact_f32");
+    g = {daL, daR, dX};
+    return true;
+}
+
 // fused GAT layer: sddvv + LeakyReLU + edge softmax + weighted aggregation in one pass.
 // REF mode keeps the attention factored (p per edge, q per row: no normalisation pass over
 // the edges); FIXED materialises alpha (its backward needs the transposed alpha).
@@ -1065,6 +1152,13 @@ struct GatAggregate : public torch::autograd::Function<GatAggregate> {
         GatStats o;
         // the statistics only serve a backward: none without gradients (eval forwards)
         const bool grad = ctx->needs_input_grad(0) || ctx->needs_input_grad(1) || ctx->needs_input_grad(2);
+        GatExact ex;
+        if (mode == GALA_SOFTMAX_FIXED && grad && exact_stats_layer(li, x.size(0)) &&
+            gat_forward_exact(s, l, r, x, {}, {}, heads, slope, ex)) {
+            ctx->saved_data["exact"] = true;
+            ctx->save_for_backward({l, r, x, ex.lse, ex.Y, ex.Ym, ex.sma});
+            return ex.Y;
+        }
         if (recompute && grad && rowstats_enabled() && gat_forward_stats(s, l, r, x, {}, {}, heads, slope, o)) {
             ctx->saved_data["stats"] = true;
             ctx->save_for_backward({l, r, x, o.q, o.Y, o.Ym, o.sma, o.p});
@@ -1085,6 +1179,15 @@ struct GatAggregate : public torch::autograd::Function<GatAggregate> {
         const int heads = (int)ctx->saved_data["heads"].toInt();
         auto l = sv[0], r = sv[1], x = sv[2];
         GatGrads g;
+        if (ctx->saved_data.count("exact")) {
+            const GatExact ex{sv[4], sv[3], sv[5], sv[6], r};
+            if (!gat_backward_exact(l, ex, x, grad_outputs[0], li, slope, heads, g)) {
+                auto alpha = torch::empty({slot(2 * li).cols.numel() * heads}, fopts(x));  // rebuild alpha
+                gat_forward_launch(slot(2 * li), l, r, x, {}, {}, heads, slope, mode, alpha.data_ptr<float>(), nullptr);
+                g = gat_backward(l, r, x, alpha, {}, grad_outputs[0], li, slope, mode, heads, {}, {});
+            }
+            return {g.daL.view_as(l), g.daR.view_as(r), g.dX, torch::Tensor(), torch::Tensor(), torch::Tensor()};
+        }
         if (ctx->saved_data.count("stats")) {
             const GatStats o{sv[4], sv[3], sv[5], sv[6], r, sv[7]};
             if (!gat_backward_stats(l, o, grad_outputs[0], li, slope, heads, g) &&
@@ -1151,6 +1254,14 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
         GatStats o;
         const bool grad = ctx->needs_input_grad(0) || ctx->needs_input_grad(1) || ctx->needs_input_grad(2) ||
                           ctx->needs_input_grad(3);
+        GatExact ex;
+        if (mode == GALA_SOFTMAX_FIXED && grad && exact_stats_layer(li, x.size(0)) &&
+            gat_forward_exact(s, l, {}, x, w, b, heads, slope, ex)) {
+            // ex.aR: the recomputed source logits, the backward's second operand of every logit
+            ctx->saved_data["exact"] = true;
+            ctx->save_for_backward({l, x, w, b_saved, ex.aR, ex.lse, ex.Y, ex.Ym, ex.sma});
+            return ex.Y;
+        }
         if (recompute && grad && rowstats_enabled() && gat_forward_stats(s, l, {}, x, w, b, heads, slope, o)) {
             // o.aR: the recomputed source logits, read by the backward
             ctx->saved_data["stats"] = true;
@@ -1169,7 +1280,8 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
         auto sv = ctx->get_saved_variables();
         auto l = sv[0], x = sv[1], w = sv[2], alpha = sv[4];
         const bool stats = ctx->saved_data.count("stats") > 0;
-        torch::Tensor q = stats ? sv[5] : (sv[5].numel() > 0 ? sv[5] : torch::Tensor());
+        const bool exact = ctx->saved_data.count("exact") > 0;   // sv[4..8] = aR, lse, Y, Ym, sma
+        torch::Tensor q = stats ? sv[5] : ((!exact && sv[5].numel() > 0) ? sv[5] : torch::Tensor());
         const bool has_bias = ctx->saved_data["has_bias"].toBool();
         const int heads = (int)ctx->saved_data["heads"].toInt();
         const int64_t li = ctx->saved_data["li"].toInt(), mode = ctx->saved_data["mode"].toInt();
@@ -1177,6 +1289,15 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
         torch::Tensor b = has_bias ? sv[3] : torch::Tensor();
         GatGrads g;
         bool done = false, fused_linear = false;
+        if (exact) {
+            const GatExact ex{sv[6], sv[5], sv[7], sv[8], sv[4]};
+            done = gat_backward_exact(l, ex, x, grad_outputs[0], li, slope, heads, g);
+            alpha = torch::empty({0}, fopts(x));
+            if (!done) {  // rebuild alpha for the alpha-storing backward
+                alpha = torch::empty({slot(2 * li).cols.numel() * heads}, fopts(x));
+                gat_forward_launch(slot(2 * li), l, {}, x, w, b, heads, slope, mode, alpha.data_ptr<float>(), nullptr);
+            }
+        }
         if (stats) {
             const GatStats o{sv[6], q, sv[7], sv[8], sv[4], sv[9]};
             // several heads: the Linear's dX term goes into the kernel's dX store
@@ -1186,7 +1307,7 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
             fused_linear = fused_linear && done;
             alpha = torch::empty({0}, fopts(x));  // otherwise: the recomputed path below
         }
-        if (!done && alpha.numel() == 0 && !gat_backward_recompute(l, {}, x, q, grad_outputs[0], li, slope, heads, w, b, g)) {
+        if (!done && !exact && alpha.numel() == 0 && !gat_backward_recompute(l, {}, x, q, grad_outputs[0], li, slope, heads, w, b, g)) {
             if (stats) q = q.clone();
             alpha = torch::empty({slot(2 * li).cols.numel() * heads}, fopts(x));
             gat_forward_launch(slot(2 * li), l, {}, x, w, b, heads, slope, mode, alpha.data_ptr<float>(),

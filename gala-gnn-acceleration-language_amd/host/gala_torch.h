@@ -80,6 +80,9 @@ struct GraphSlots {
     std::vector<std::shared_ptr<SplitState>> split;  // hub-row plans (nullptr: none)
     std::vector<std::shared_ptr<MergedCsr>> merged;  // tiled graphs' merged rows (nullptr: none)
     std::vector<std::shared_ptr<PatternT>> pattern_t;  // transposed patterns (built on first use)
+    // slot i holds slot i-1's pattern, element for element (-1: not compared yet).  Slots are only
+    // appended until clear(), so the answer stays with the index
+    std::vector<int8_t> holds_previous;
     int64_t nrows = 0;
     int ra = 5, rb = 7;    // kernel-sampling coefficients (common.h:813-833)
     int nsamples = 0;      // 0 = no kernel sampling

@@ -96,6 +96,21 @@ int gala_cpu_gat_bwd_stats_f32(const gala_csr_t *A, const float *aL, const float
                                float slope, const float *q, const float *Y, int64_t ldy,
                                const float *Ym, int64_t ldym, const float *sma, float *dX,
                                int64_t lddx, float *d_aL, void *stream);
+/* the exact pair (gala_hip.h): the kernels' sums in the kernels' association -- U-edge batches
+ * with one max rescale each, hub rows of A's plan as chunk partials (its threshold and chunk;
+ * no workspace is read), the dots over the lanes' shares and their xor butterfly.  The lane
+ * layout follows the row strides as the kernels pick it for 16-byte aligned arrays; a device
+ * array aligned to less makes the kernels take narrower vectors, and the dots' association
+ * then differs from the twins' (the values stay within the same bounds) */
+int gala_cpu_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
+                                     const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
+                                     float slope, float *Y, int64_t ldy, float *lse, float *Ym, int64_t ldym,
+                                     float *sma, float *aR_out, void *stream);
+int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *X,
+                                     int64_t ldx, const float *dY, int64_t lddy, int32_t F, int32_t heads,
+                                     float slope, const float *lse, const float *Y, int64_t ldy,
+                                     const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
+                                     int64_t lddx, float *d_aL, float *d_aR, void *stream);
 int gala_cpu_gat_fwd_stats_ex_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
                                   const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
                                   float slope, float *Y, int64_t ldy, float *q_out, float *Ym, int64_t ldym,

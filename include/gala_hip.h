@@ -447,6 +447,38 @@ int gala_gat_bwd_stats_f32(const gala_csr_t *A, const float *aL, const float *aR
                            int64_t ldym, const float *sma, float *dX, int64_t lddx, float *d_aL,
                            void *stream);
 /*
+ * The exact pair: the layer with the stable softmax of GALA_SOFTMAX_FIXED and its true
+ * gradients, from row statistics, for a square pattern that is symmetric (edge (r, c) present
+ * iff (c, r) is; the caller asserts it -- gala.ops tests it).  Per head, with
+ * s = LeakyReLU(fl(aL[r] + aR[c])), m = 1 where the sum is positive, else slope:
+ *   forward:  alpha_rc = exp(s - lse[r]), lse[r] = max_c s + log sum_c exp(s - max);
+ *             Y, Ym = sum_c m alpha X[c], sma = sum_c m alpha, lse ([n, heads]; an empty
+ *             row: zeros).  aR, or (aR NULL) its recompute from X (wR, bR); aR_out then
+ *             receives the rows' source logits, which the backward must be given as aR.
+ *   backward: g[r] = <dY[r], Y[r]>_h;  d_aL[r] = <dY[r], Ym[r]>_h - g[r] sma[r];
+ *             dX[c] = sum_r alpha_rc dY[r];  d_aR[c] = <sum_r m alpha_rc dY[r], X[c]>_h -
+ *             sum_r m alpha_rc g[r], the sums over row c's neighbours r.  One gather of dY
+ *             rows and one 16-byte side line {aL, lse, g, 0} per edge and head; no stored
+ *             alpha and no transposed graph.  side: scratch of n_rows * heads * 4 floats,
+ *             16-byte aligned.
+ * Sums run in CSR order; hub rows of the graph's plan are summed as chunk partials combined
+ * in ascending chunk order (forward: with the max rescale) from the plan's workspace, which
+ * holds 2F + 3 heads (forward) or 2F + heads (backward) floats per chunk -- a plan with hub
+ * rows whose workspace is missing or smaller gives GALA_ERR_INVALID_ARG, nothing launched.
+ * No atomics: results are bit-identical run to run.  Shapes as the REF statistics pair
+ * (several heads need D/VEC a power of two, at most 64 vectors per row; else
+ * GALA_ERR_UNSUPPORTED); a pattern that is not square is GALA_ERR_INVALID_ARG.
+ */
+int gala_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
+                                 const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
+                                 float slope, float *Y, int64_t ldy, float *lse, float *Ym, int64_t ldym,
+                                 float *sma, float *aR_out, void *stream);
+int gala_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *X,
+                                 int64_t ldx, const float *dY, int64_t lddy, int32_t F, int32_t heads,
+                                 float slope, const float *lse, const float *Y, int64_t ldy,
+                                 const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
+                                 int64_t lddx, float *d_aL, float *d_aR, void *stream);
+/*
  * The same pair over a gathered feature table (a row partition's halo, gala/dist.py
  * HaloGat): the pattern's columns index the table (n_cols >= n_rows), so a row is no longer
  * its own column.  gala_gat_fwd_stats_ex_f32: self_col[r] = the table column of row r's own
