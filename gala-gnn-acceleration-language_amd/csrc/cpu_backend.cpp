@@ -1115,17 +1115,24 @@ constexpr int kExactU = 8;  // edges per batch (one max rescale each)
 
 }  // namespace
 
-extern "C" int gala_cpu_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR,
-                                                const float *wR, const float *bR, const float *X, int64_t ldx,
-                                                int32_t F, int32_t heads, float slope, float *Y, int64_t ldy,
-                                                float *lse, float *Ym, int64_t ldym, float *sma, float *aR_out,
-                                                void *) {
+// self_col NULL: a square pattern (row r is column r); else the columns index gathered tables
+static int exact_pattern_ok(const gala_csr_t *A, const int32_t *self_col) {
+    if (A->n_rows > A->n_cols || (!self_col && A->n_cols != A->n_rows)) return GALA_ERR_INVALID_ARG;
+    return GALA_OK;
+}
+
+extern "C" int gala_cpu_gat_fwd_stats_exact_ex_f32(const gala_csr_t *A, const float *aL, const float *aR,
+                                                   const float *wR, const float *bR, const float *X, int64_t ldx,
+                                                   int32_t F, int32_t heads, float slope, float *Y, int64_t ldy,
+                                                   float *lse, float *Ym, int64_t ldym, float *sma,
+                                                   const int32_t *self_col, float *aR_out, void *) {
     int st = check_csr(A);
     if (st) return st;
     if (heads < 1 || F < 1 || F % heads != 0 || ldx < F || ldy < F || ldym < F) return GALA_ERR_INVALID_ARG;
     if (A->n_rows == 0) return GALA_OK;
+    if ((st = exact_pattern_ok(A, self_col))) return st;
     if (!aL || (!aR && !wR) || !Y || !lse || !Ym || !sma || !X) return GALA_ERR_INVALID_ARG;
-    if (A->n_cols != A->n_rows || (aR_out && aR)) return GALA_ERR_INVALID_ARG;
+    if (aR_out && aR) return GALA_ERR_INVALID_ARG;
     ExactShape sh;
     if ((st = exact_shape(F, heads, {ldx, ldy, ldym}, &sh))) return st;
     const int32_t H = heads, D = F / H;
@@ -1137,7 +1144,11 @@ extern "C" int gala_cpu_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float
             for (int32_t h = 0; h < H; ++h)
                 rc[(size_t)j * H + h] = exact_lane_dot(wR + h * D, X + j * ldx + h * D, D, sh) + (bR ? bR[h] : 0.0f);
         aR = rc.data();
-        if (aR_out) std::copy(rc.begin(), rc.end(), aR_out);
+        if (aR_out)  // the own columns' logits (column-indexed)
+            for (int64_t r = 0; r < A->n_rows; ++r) {
+                const int64_t s = self_col ? self_col[r] : r;
+                std::copy(rc.begin() + s * H, rc.begin() + (s + 1) * H, aR_out + s * H);
+            }
     }
 #pragma omp parallel
     {
@@ -1220,41 +1231,47 @@ extern "C" int gala_cpu_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float
     return GALA_OK;
 }
 
-extern "C" int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR,
-                                                const float *X, int64_t ldx, const float *dY, int64_t lddy,
-                                                int32_t F, int32_t heads, float slope, const float *lse,
-                                                const float *Y, int64_t ldy, const float *Ym, int64_t ldym,
-                                                const float *sma, float *side, float *dX, int64_t lddx,
-                                                float *d_aL, float *d_aR, void *) {
-    int st = check_csr(A);
-    if (st) return st;
-    if (heads < 1 || F < 1 || F % heads != 0 || ldx < F || lddy < F || ldy < F || ldym < F || lddx < F)
-        return GALA_ERR_INVALID_ARG;
-    if (A->n_rows == 0) return GALA_OK;
-    if (!aL || !aR || !X || !dY || !lse || !Y || !Ym || !sma || !side || !dX || !d_aL || !d_aR)
-        return GALA_ERR_INVALID_ARG;
-    if (A->n_cols != A->n_rows) return GALA_ERR_INVALID_ARG;
-    ExactShape sh;
-    if ((st = exact_shape(F, heads, {ldx, lddy, ldy, ldym, lddx}, &sh))) return st;
-    const int32_t H = heads, D = F / H;
-    // the row-local pre-pass: g, d_aL and the side lines {aL, lse, g, 0}
+extern "C" int gala_cpu_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR,
+                                                const float *wR, const float *bR, const float *X, int64_t ldx,
+                                                int32_t F, int32_t heads, float slope, float *Y, int64_t ldy,
+                                                float *lse, float *Ym, int64_t ldym, float *sma, float *aR_out,
+                                                void *) {
+    return gala_cpu_gat_fwd_stats_exact_ex_f32(A, aL, aR, wR, bR, X, ldx, F, heads, slope, Y, ldy, lse, Ym, ldym,
+                                               sma, nullptr, aR_out, nullptr);
+}
+
+namespace {
+
+// the row-local pre-pass: g, d_aL and the side lines {aL, lse, g, 0} at the rows' own columns
+void exact_pre_pass(const gala_csr_t *A, const ExactShape &sh, const float *aL, const float *dY_rows, int64_t lddy,
+                    int32_t F, int32_t H, const float *lse, const float *Y, int64_t ldy, const float *Ym,
+                    int64_t ldym, const float *sma, const int32_t *self_col, float *side, float *d_aL) {
+    const int32_t D = F / H;
 #pragma omp parallel for schedule(static, 1024)
     for (int64_t r = 0; r < A->n_rows; ++r)
         for (int32_t h = 0; h < H; ++h) {
             const int64_t o = r * H + h;
-            const float g = exact_lane_dot(dY + r * lddy + h * D, Y + r * ldy + h * D, D, sh);
-            const float s1 = exact_lane_dot(dY + r * lddy + h * D, Ym + r * ldym + h * D, D, sh);
+            const float g = exact_lane_dot(dY_rows + r * lddy + h * D, Y + r * ldy + h * D, D, sh);
+            const float s1 = exact_lane_dot(dY_rows + r * lddy + h * D, Ym + r * ldym + h * D, D, sh);
             d_aL[o] = s1 - g * sma[o];
-            side[o * 4 + 0] = aL[o], side[o * 4 + 1] = lse[o], side[o * 4 + 2] = g, side[o * 4 + 3] = 0.0f;
+            float *sd = side + (((self_col ? (int64_t)self_col[r] : r) * H) + h) * 4;
+            sd[0] = aL[o], sd[1] = lse[o], sd[2] = g, sd[3] = 0.0f;
         }
-    // the gather pass: row c over its neighbours r
+}
+
+// the gather pass: row c over its neighbours r (table columns), s = row c's own column
+void exact_gather_pass(const gala_csr_t *A, const ExactShape &sh, const float *aR, const float *X, int64_t ldx,
+                       const float *dY, int64_t lddy, int32_t F, int32_t H, float slope, const float *side,
+                       const int32_t *self_col, float *dX, int64_t lddx, float *d_aR) {
+    const int32_t D = F / H;
 #pragma omp parallel
     {
         std::vector<float> dx((size_t)D), dxm((size_t)D), pa((size_t)D), pam((size_t)D);
 #pragma omp for schedule(dynamic, kRowChunk)
         for (int64_t c = 0; c < A->n_rows; ++c)
             for (int32_t h = 0; h < H; ++h) {
-                const float ar = aR[c * H + h];
+                const int64_t s = self_col ? (int64_t)self_col[c] : c;
+                const float ar = aR[s * H + h];
                 auto range = [&](int64_t e0, int64_t e1, float *a, float *am, float &sg) {
                     for (int64_t e = e0; e < e1; ++e) {
                         const int64_t r = A->col[e];
@@ -1291,9 +1308,66 @@ extern "C" int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float
                     for (int32_t f = 0; f < D; ++f) dx[f] = dx[f] + pa[f], dxm[f] = dxm[f] + pam[f];
                 });
                 for (int32_t f = 0; f < D; ++f) dX[c * lddx + h * D + f] = dx[f];
-                d_aR[c * H + h] = exact_lane_dot(dxm.data(), X + c * ldx + h * D, D, sh) - sg;
+                d_aR[c * H + h] = exact_lane_dot(dxm.data(), X + s * ldx + h * D, D, sh) - sg;
             }
     }
+}
+
+}  // namespace
+
+extern "C" int gala_cpu_gat_bwd_exact_pre_ex_f32(const gala_csr_t *A, const float *aL, const float *dY_rows,
+                                                 int64_t lddy, int32_t F, int32_t heads, const float *lse,
+                                                 const float *Y, int64_t ldy, const float *Ym, int64_t ldym,
+                                                 const float *sma, const int32_t *self_col, float *side, float *d_aL,
+                                                 void *) {
+    int st = check_csr(A);
+    if (st) return st;
+    if (heads < 1 || F < 1 || F % heads != 0 || lddy < F || ldy < F || ldym < F) return GALA_ERR_INVALID_ARG;
+    if (A->n_rows == 0) return GALA_OK;
+    if ((st = exact_pattern_ok(A, self_col))) return st;
+    if (!side || ((uintptr_t)side % 16) != 0) return GALA_ERR_INVALID_ARG;
+    if (!aL || !dY_rows || !lse || !Y || !Ym || !sma || !d_aL) return GALA_ERR_INVALID_ARG;
+    ExactShape sh;
+    if ((st = exact_shape(F, heads, {lddy, ldy, ldym}, &sh))) return st;
+    exact_pre_pass(A, sh, aL, dY_rows, lddy, F, heads, lse, Y, ldy, Ym, ldym, sma, self_col, side, d_aL);
+    return GALA_OK;
+}
+
+extern "C" int gala_cpu_gat_bwd_exact_gather_ex_f32(const gala_csr_t *A, const float *aR, const float *X, int64_t ldx,
+                                                    const float *dY, int64_t lddy, int32_t F, int32_t heads,
+                                                    float slope, const float *side, const int32_t *self_col,
+                                                    float *dX, int64_t lddx, float *d_aR, void *) {
+    int st = check_csr(A);
+    if (st) return st;
+    if (heads < 1 || F < 1 || F % heads != 0 || ldx < F || lddy < F || lddx < F) return GALA_ERR_INVALID_ARG;
+    if (A->n_rows == 0) return GALA_OK;
+    if ((st = exact_pattern_ok(A, self_col))) return st;
+    if (!side || ((uintptr_t)side % 16) != 0) return GALA_ERR_INVALID_ARG;
+    if (!aR || !X || !dY || !dX || !d_aR) return GALA_ERR_INVALID_ARG;
+    ExactShape sh;
+    if ((st = exact_shape(F, heads, {ldx, lddy, lddx}, &sh))) return st;
+    exact_gather_pass(A, sh, aR, X, ldx, dY, lddy, F, heads, slope, side, self_col, dX, lddx, d_aR);
+    return GALA_OK;
+}
+
+extern "C" int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR,
+                                                const float *X, int64_t ldx, const float *dY, int64_t lddy,
+                                                int32_t F, int32_t heads, float slope, const float *lse,
+                                                const float *Y, int64_t ldy, const float *Ym, int64_t ldym,
+                                                const float *sma, float *side, float *dX, int64_t lddx,
+                                                float *d_aL, float *d_aR, void *) {
+    int st = check_csr(A);
+    if (st) return st;
+    if (heads < 1 || F < 1 || F % heads != 0 || ldx < F || lddy < F || ldy < F || ldym < F || lddx < F)
+        return GALA_ERR_INVALID_ARG;
+    if (A->n_rows == 0) return GALA_OK;
+    if (!aL || !aR || !X || !dY || !lse || !Y || !Ym || !sma || !side || !dX || !d_aL || !d_aR)
+        return GALA_ERR_INVALID_ARG;
+    if (A->n_cols != A->n_rows) return GALA_ERR_INVALID_ARG;
+    ExactShape sh;
+    if ((st = exact_shape(F, heads, {ldx, lddy, ldy, ldym, lddx}, &sh))) return st;
+    exact_pre_pass(A, sh, aL, dY, lddy, F, heads, lse, Y, ldy, Ym, ldym, sma, nullptr, side, d_aL);
+    exact_gather_pass(A, sh, aR, X, ldx, dY, lddy, F, heads, slope, side, nullptr, dX, lddx, d_aR);
     return GALA_OK;
 }
 

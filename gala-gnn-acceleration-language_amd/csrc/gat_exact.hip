@@ -26,7 +26,14 @@ struct ExactDev {
     const float *lse;    // backward pre-pass [n, H]
     float *side;         // backward: [n, H, 4] = {aL, lse, g, 0}
     float *d_aR;         // backward [n, H]
+    // the column of each row's own vertex when the pattern's columns index gathered tables
+    // (X, aR, dY and side are then [n_cols, ...]); NULL: the row itself (square pattern)
+    const int32_t *self_col;
 };
+
+__device__ __forceinline__ int64_t own_col(const ExactDev &x, int64_t row) {
+    return x.self_col ? (int64_t)x.self_col[row] : row;
+}
 
 template <int VEC, int CH>
 struct ExFwdState {
@@ -190,11 +197,12 @@ __global__ __launch_bounds__(kBlock) void k_gat_exact_fwd(EdgeParams p, GatDev d
         if (d.ar_out) {
             typedef typename GVec<VEC>::T V;
             V xr[CH];
+            const int64_t s = own_col(x, row);
 #pragma unroll
             for (int ch = 0; ch < CH; ++ch)
-                xr[ch] = mask_pad<VEC>(gl_.ln.nv[ch], *reinterpret_cast<const V *>(d.X + row * d.ldx + gl_.ln.off[ch]));
+                xr[ch] = mask_pad<VEC>(gl_.ln.nv[ch], *reinterpret_cast<const V *>(d.X + s * d.ldx + gl_.ln.off[ch]));
             const float a = __fadd_rn(attn_dot<HW, VEC, CH>(gl_.w, xr), gl_.wb);
-            if (gl_.leader) d.ar_out[row * gl_.H + gl_.hh] = a;
+            if (gl_.leader) d.ar_out[s * gl_.H + gl_.hh] = a;
         }
     }
     if (hub_row(p, split_threshold, row)) return;  // k_gat_exact_fwd_chunk / _fixup
@@ -299,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void k_gat_exact_bwd_pre(EdgeParams p, GatD
     typedef float F4 __attribute__((ext_vector_type(4)));
     F4 line;
     line.x = gl_.al, line.y = x.lse[o], line.z = g, line.w = 0.0f;
-    *reinterpret_cast<F4 *>(x.side + o * 4) = line;
+    *reinterpret_cast<F4 *>(x.side + (own_col(x, row) * gl_.H + gl_.hh) * 4) = line;
 }
 
 template <int VEC, int CH>
@@ -379,17 +387,17 @@ __device__ __forceinline__ void exact_bwd_range(const EdgeParams &p, const GatDe
     }
 }
 
-// dX[c] and d_aR[c] = <dXm[c], X[c]>_h - sg[c]
+// dX[c] and d_aR[c] = <dXm[c], X[c]>_h - sg[c]; s: the table column of row c's own vertex
 template <int G, int VEC, int CH, int HW>
 __device__ __forceinline__ void exact_bwd_store(const GatDev &d, const ExactDev &x,
-                                                const GatLane<G, VEC, CH, false> &gl_, int64_t row,
+                                                const GatLane<G, VEC, CH, false> &gl_, int64_t row, int64_t s,
                                                 const ExBwdState<VEC, CH> &st) {
     typedef typename GVec<VEC>::T V;
     exact_store_row<G, VEC, CH>(gl_.ln, d.dX + row * d.lddx, st.dx, 1.0f);
     float dot = 0.0f;
 #pragma unroll
     for (int ch = 0; ch < CH; ++ch) {
-        const V xr = mask_pad<VEC>(gl_.ln.nv[ch], *reinterpret_cast<const V *>(d.X + row * d.ldx + gl_.ln.off[ch]));
+        const V xr = mask_pad<VEC>(gl_.ln.nv[ch], *reinterpret_cast<const V *>(d.X + s * d.ldx + gl_.ln.off[ch]));
         const float *xv = reinterpret_cast<const float *>(&xr);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) dot = fmaf(st.dxm[ch][i], xv[i], dot);
@@ -404,21 +412,22 @@ __global__ __launch_bounds__(kBlock) void k_gat_exact_bwd(EdgeParams p, GatDev d
     GALA_ROW_PROLOGUE(G);
     if (!row_ok) return;
     if (hub_row(p, split_threshold, row)) return;  // k_gat_exact_bwd_chunk / _fixup
-    const GatLane<G, VEC, CH, false> gl_(p, d, gl, row);  // d.aL = aR: al = aR[row, h]
+    const int64_t own = own_col(x, row);
+    const GatLane<G, VEC, CH, false> gl_(p, d, gl, own);  // d.aL = the aR table: al = aR[own, h]
     ExBwdState<VEC, CH> st;
     for (int s = 0; s < p.seg.n; ++s) {
         int64_t e0, e1;
         row_range(p, s, row, e0, e1);
         exact_bwd_range<G, VEC, U, CH, HW>(p, d, x, gl_, e0, e1, st);
     }
-    exact_bwd_store<G, VEC, CH, HW>(d, x, gl_, row, st);
+    exact_bwd_store<G, VEC, CH, HW>(d, x, gl_, row, own, st);
 }
 
 // hub rows, backward: chunk partials -> ws[c] = {dX[F], dXm[F], sg[H]}
 template <int G, int VEC, int U, int CH, int HW>
 __global__ __launch_bounds__(kBlock) void k_gat_exact_bwd_chunk(EdgeParams p, GatDev d, ExactDev x, HubSplit sp) {
     GALA_CHUNK_PROLOGUE(G);
-    const GatLane<G, VEC, CH, false> gl_(p, d, gl, row);
+    const GatLane<G, VEC, CH, false> gl_(p, d, gl, own_col(x, row));
     ExBwdState<VEC, CH> st;
     exact_bwd_range<G, VEC, U, CH, HW>(p, d, x, gl_, e0, e1, st);
     float *w = sp.ws + c * sp.ws_cols;
@@ -441,7 +450,8 @@ __global__ __launch_bounds__(kBlock) void k_gat_exact_bwd_fixup(EdgeParams p, Ga
     const int64_t ri = ((int64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave) * (kWave / G) + lane / G;
     if (ri >= sp.n_rows_split) return;
     const int64_t row = sp.rows[ri];
-    const GatLane<G, VEC, CH, false> gl_(p, d, gl, row);
+    const int64_t s = own_col(x, row);
+    const GatLane<G, VEC, CH, false> gl_(p, d, gl, s);
     const int F = d.F;
     ExBwdState<VEC, CH> st;
     for (int64_t cc = sp.row_chunk0[ri]; cc < sp.row_chunk0[ri + 1]; ++cc) {
@@ -456,7 +466,7 @@ __global__ __launch_bounds__(kBlock) void k_gat_exact_bwd_fixup(EdgeParams p, Ga
                 st.dxm[ch][i] = __fadd_rn(st.dxm[ch][i], in ? w[F + gl_.ln.off[ch] + i] : 0.0f);
             }
     }
-    exact_bwd_store<G, VEC, CH, HW>(d, x, gl_, row, st);
+    exact_bwd_store<G, VEC, CH, HW>(d, x, gl_, row, s, st);
 }
 
 }  // namespace gala
@@ -471,6 +481,7 @@ struct ExactArgs {
     ExactDev x;
     HubSplit sp;
     bool split, bwd;
+    bool pre = true, gather = true;  // the backward's two passes (the _ex calls run one each)
     hipStream_t hs;
 };
 
@@ -494,7 +505,8 @@ void launch_exact(const ExactArgs &a) {
         // the pre-pass reads the rows' aL (d.aL); the gather the rows' aR in its place
         ExactArgs g = a;
         g.d.aL = a.d.aR;
-        hipLaunchKernelGGL((k_gat_exact_bwd_pre<G, VEC, CH, HW>), rows, blk, 0, a.hs, a.p, a.d, a.x);
+        if (a.pre) hipLaunchKernelGGL((k_gat_exact_bwd_pre<G, VEC, CH, HW>), rows, blk, 0, a.hs, a.p, a.d, a.x);
+        if (!a.gather) return;
         hipLaunchKernelGGL((k_gat_exact_bwd<G, VEC, U, CH, HW>), rows, blk, 0, a.hs, g.p, g.d, g.x, thr);
         if (!a.split) return;
         hipLaunchKernelGGL((k_gat_exact_bwd_chunk<G, VEC, U, CH, HW>), dim3(blocks_for_groups(a.sp.n_chunks, G)), blk,
@@ -557,10 +569,10 @@ int exact_dispatch(const gala_csr_t *A, ExactArgs &a, int F, int heads, int vec,
     if (heads > 1 && (hw == 0 || (hw & (hw - 1)))) return GALA_ERR_UNSUPPORTED;
     // a graph with hub rows brings the workspace their chunk partials need
     const gala_split_plan_t *plan = A->split;
-    if (plan && plan->n_chunks > 0 && plan->n_rows_split > 0 && A->n_seg == 1 &&
+    if (ws_need > 0 && plan && plan->n_chunks > 0 && plan->n_rows_split > 0 && A->n_seg == 1 &&
         (!plan->workspace || plan->ws_cols < ws_need))
         return GALA_ERR_INVALID_ARG;
-    a.split = hub_split(A, ws_need, &a.sp);
+    a.split = ws_need > 0 && hub_split(A, ws_need, &a.sp);
     int r;
     if (rc && a.bwd) return GALA_ERR_INVALID_ARG;  // the backward reads aR: it has no recompute
     if (vec == 4) r = rc ? exact_vec<4, true>(a, L, ch, heads, hw) : exact_vec<4, false>(a, L, ch, heads, hw);
@@ -574,17 +586,26 @@ inline bool aligned_to(const void *ptr, int v) { return ((uintptr_t)ptr % (4 * v
 
 }  // namespace
 
-extern "C" int gala_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
-                                            const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
-                                            float slope, float *Y, int64_t ldy, float *lse, float *Ym, int64_t ldym,
-                                            float *sma, float *aR_out, void *stream) {
+// self_col NULL needs a square pattern (a row is then its own column); with it the columns
+// index gathered tables of n_cols >= n_rows rows
+static int exact_pattern_ok(const gala_csr_t *A, const int32_t *self_col) {
+    if (A->n_rows > A->n_cols) return GALA_ERR_INVALID_ARG;
+    if (!self_col && A->n_cols != A->n_rows) return GALA_ERR_INVALID_ARG;
+    return GALA_OK;
+}
+
+extern "C" int gala_gat_fwd_stats_exact_ex_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
+                                               const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
+                                               float slope, float *Y, int64_t ldy, float *lse, float *Ym,
+                                               int64_t ldym, float *sma, const int32_t *self_col, float *aR_out,
+                                               void *stream) {
     ExactArgs a{};
     int st = edge_setup(A, heads, &a.p);
     if (st) return st;
     if (F < 1 || F % heads != 0 || ldx < F || ldy < F || ldym < F) return GALA_ERR_INVALID_ARG;
     if (A->n_rows == 0) return GALA_OK;
+    if ((st = exact_pattern_ok(A, self_col))) return st;
     if (!aL || (!aR && !wR) || !Y || !lse || !Ym || !sma || !X) return GALA_ERR_INVALID_ARG;
-    if (A->n_cols != A->n_rows) return GALA_ERR_INVALID_ARG;  // a square, symmetric pattern
     if (aR_out && aR) return GALA_ERR_INVALID_ARG;
     const int D = F / heads;
     auto ok = [&](int v) {
@@ -598,39 +619,104 @@ extern "C" int gala_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL
     a.d.aL = aL, a.d.aR = aR, a.d.wR = rc ? wR : nullptr, a.d.bR = rc ? bR : nullptr;
     a.d.X = X, a.d.ldx = ldx, a.d.F = F, a.d.slope = slope;
     a.d.Y = Y, a.d.ldy = ldy, a.d.ym_out = Ym, a.d.ldym = ldym, a.d.sma_out = sma, a.d.ar_out = aR_out;
-    a.x.lse_out = lse;
+    a.x.lse_out = lse, a.x.self_col = self_col;
     a.hs = (hipStream_t)stream;
     a.bwd = false;
     return exact_dispatch(A, a, F, heads, vec, rc, 2 * (int64_t)F + 3 * heads);
 }
+
+extern "C" int gala_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
+                                            const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
+                                            float slope, float *Y, int64_t ldy, float *lse, float *Ym, int64_t ldym,
+                                            float *sma, float *aR_out, void *stream) {
+    return gala_gat_fwd_stats_exact_ex_f32(A, aL, aR, wR, bR, X, ldx, F, heads, slope, Y, ldy, lse, Ym, ldym, sma,
+                                           nullptr, aR_out, stream);
+}
+
+namespace {
+
+// The backward's operands; pre / gather: the passes to run.  One vector width serves every
+// operand a pass reads (dY_rows and the dY table too: the own block of a table whose rows are
+// no multiple of 16 bytes may start off the table's alignment).
+struct ExactBwd {
+    const float *aL, *aR, *X, *dY, *dY_rows, *lse, *Y, *Ym, *sma;
+    int64_t ldx, lddy, ldy, ldym, lddx;
+    const int32_t *self_col;
+    float *side, *dX, *d_aL, *d_aR;
+};
+
+int exact_backward(const gala_csr_t *A, const ExactBwd &b, int32_t F, int32_t heads, float slope, bool pre,
+                   bool gather, void *stream) {
+    ExactArgs a{};
+    int st = edge_setup(A, heads, &a.p);
+    if (st) return st;
+    if (F < 1 || F % heads != 0 || b.lddy < F) return GALA_ERR_INVALID_ARG;
+    if (pre && (b.ldy < F || b.ldym < F)) return GALA_ERR_INVALID_ARG;
+    if (gather && (b.ldx < F || b.lddx < F)) return GALA_ERR_INVALID_ARG;
+    if (A->n_rows == 0) return GALA_OK;
+    if ((st = exact_pattern_ok(A, b.self_col))) return st;
+    if (!b.side || ((uintptr_t)b.side % 16) != 0) return GALA_ERR_INVALID_ARG;
+    if (pre && (!b.aL || !b.dY_rows || !b.lse || !b.Y || !b.Ym || !b.sma || !b.d_aL)) return GALA_ERR_INVALID_ARG;
+    if (gather && (!b.aR || !b.X || !b.dY || !b.dX || !b.d_aR)) return GALA_ERR_INVALID_ARG;
+    const int D = F / heads;
+    auto ok = [&](int v) {
+        bool padded = heads == 1 && b.lddy >= pad_to(F, v);
+        bool mult = b.lddy % v == 0;
+        if (pre) {
+            padded = padded && b.ldy >= pad_to(F, v) && b.ldym >= pad_to(F, v);
+            mult = mult && b.ldy % v == 0 && b.ldym % v == 0 && aligned_to(b.dY_rows, v) && aligned_to(b.Y, v) &&
+                   aligned_to(b.Ym, v);
+        }
+        if (gather) {
+            padded = padded && b.ldx >= pad_to(F, v) && b.lddx >= pad_to(F, v);
+            mult = mult && b.ldx % v == 0 && b.lddx % v == 0 && aligned_to(b.X, v) && aligned_to(b.dY, v) &&
+                   aligned_to(b.dX, v);
+        }
+        return (D % v == 0 || padded) && mult;
+    };
+    int vec = 4;
+    while (vec > 1 && !ok(vec)) vec >>= 1;
+    a.d.aL = b.aL, a.d.aR = b.aR, a.d.X = b.X, a.d.ldx = b.ldx, a.d.F = F, a.d.slope = slope;
+    a.d.dY = b.dY, a.d.dy_rows = b.dY_rows, a.d.lddy = b.lddy, a.d.ys = b.Y, a.d.ldy = b.ldy, a.d.yms = b.Ym;
+    a.d.ldym = b.ldym, a.d.smas = b.sma;
+    a.d.dX = b.dX, a.d.lddx = b.lddx, a.d.d_aL = b.d_aL;
+    a.x.lse = b.lse, a.x.side = b.side, a.x.d_aR = b.d_aR, a.x.self_col = b.self_col;
+    a.hs = (hipStream_t)stream;
+    a.bwd = true, a.pre = pre, a.gather = gather;
+    // the pre-pass is row-local: no hub chunks, no workspace
+    return exact_dispatch(A, a, F, heads, vec, false, gather ? 2 * (int64_t)F + heads : 0);
+}
+
+}  // namespace
 
 extern "C" int gala_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *X,
                                             int64_t ldx, const float *dY, int64_t lddy, int32_t F, int32_t heads,
                                             float slope, const float *lse, const float *Y, int64_t ldy,
                                             const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
                                             int64_t lddx, float *d_aL, float *d_aR, void *stream) {
-    ExactArgs a{};
-    int st = edge_setup(A, heads, &a.p);
-    if (st) return st;
-    if (F < 1 || F % heads != 0 || ldx < F || lddy < F || ldy < F || ldym < F || lddx < F) return GALA_ERR_INVALID_ARG;
-    if (A->n_rows == 0) return GALA_OK;
-    if (!aL || !aR || !X || !dY || !lse || !Y || !Ym || !sma || !side || !dX || !d_aL || !d_aR)
-        return GALA_ERR_INVALID_ARG;
-    if (A->n_cols != A->n_rows || ((uintptr_t)side % 16) != 0) return GALA_ERR_INVALID_ARG;
-    const int D = F / heads;
-    auto ok = [&](int v) {
-        const bool fits = D % v == 0 || (heads == 1 && ldx >= pad_to(F, v) && lddy >= pad_to(F, v) &&
-                                         ldy >= pad_to(F, v) && ldym >= pad_to(F, v) && lddx >= pad_to(F, v));
-        return fits && ldx % v == 0 && lddy % v == 0 && ldy % v == 0 && ldym % v == 0 && lddx % v == 0 &&
-               aligned_to(X, v) && aligned_to(dY, v) && aligned_to(Y, v) && aligned_to(Ym, v) && aligned_to(dX, v);
-    };
-    int vec = 4;
-    while (vec > 1 && !ok(vec)) vec >>= 1;
-    a.d.aL = aL, a.d.aR = aR, a.d.X = X, a.d.ldx = ldx, a.d.F = F, a.d.slope = slope;
-    a.d.dY = dY, a.d.lddy = lddy, a.d.ys = Y, a.d.ldy = ldy, a.d.yms = Ym, a.d.ldym = ldym, a.d.smas = sma;
-    a.d.dX = dX, a.d.lddx = lddx, a.d.d_aL = d_aL;
-    a.x.lse = lse, a.x.side = side, a.x.d_aR = d_aR;
-    a.hs = (hipStream_t)stream;
-    a.bwd = true;
-    return exact_dispatch(A, a, F, heads, vec, false, 2 * (int64_t)F + heads);
+    ExactBwd b{};
+    b.aL = aL, b.aR = aR, b.X = X, b.dY = dY, b.dY_rows = dY, b.lse = lse, b.Y = Y, b.Ym = Ym, b.sma = sma;
+    b.ldx = ldx, b.lddy = lddy, b.ldy = ldy, b.ldym = ldym, b.lddx = lddx;
+    b.side = side, b.dX = dX, b.d_aL = d_aL, b.d_aR = d_aR;
+    return exact_backward(A, b, F, heads, slope, true, true, stream);
+}
+
+extern "C" int gala_gat_bwd_exact_pre_ex_f32(const gala_csr_t *A, const float *aL, const float *dY_rows, int64_t lddy,
+                                             int32_t F, int32_t heads, const float *lse, const float *Y, int64_t ldy,
+                                             const float *Ym, int64_t ldym, const float *sma, const int32_t *self_col,
+                                             float *side, float *d_aL, void *stream) {
+    ExactBwd b{};
+    b.aL = aL, b.dY_rows = dY_rows, b.lse = lse, b.Y = Y, b.Ym = Ym, b.sma = sma;
+    b.lddy = lddy, b.ldy = ldy, b.ldym = ldym, b.self_col = self_col, b.side = side, b.d_aL = d_aL;
+    return exact_backward(A, b, F, heads, 0.0f, true, false, stream);
+}
+
+extern "C" int gala_gat_bwd_exact_gather_ex_f32(const gala_csr_t *A, const float *aR, const float *X, int64_t ldx,
+                                                const float *dY, int64_t lddy, int32_t F, int32_t heads, float slope,
+                                                const float *side, const int32_t *self_col, float *dX, int64_t lddx,
+                                                float *d_aR, void *stream) {
+    ExactBwd b{};
+    b.aR = aR, b.X = X, b.dY = dY, b.ldx = ldx, b.lddy = lddy, b.lddx = lddx, b.self_col = self_col;
+    b.side = const_cast<float *>(side), b.dX = dX, b.d_aR = d_aR;
+    return exact_backward(A, b, F, heads, slope, false, true, stream);
 }

@@ -88,6 +88,19 @@ class HipBackend:
         return self.ops.gat_bwd_stats_exact(g, aL, aR, X, dY, lse, Y, Ym, sma, heads=heads, slope=slope,
                                             symmetric=symmetric)
 
+    def gat_stats_exact_table(self, g, aL, aR, X, heads, slope, self_col, aR_out, wR=None, bR=None):
+        """(Y, lse, Ym, sma) of the exact forward over gathered tables (gala_gat_fwd_stats_exact_ex_f32)."""
+        return self.ops.gat_stats_exact_table(g, aL, X, self_col, aR=aR, wR=wR, bR=bR, aR_out=aR_out, heads=heads,
+                                              slope=slope)
+
+    def gat_bwd_exact_pre_table(self, g, aL, dY_rows, lse, Y, Ym, sma, heads, self_col, side):
+        """d_aL, and the rows' side lines into `side` at self_col (gala_gat_bwd_exact_pre_ex_f32)."""
+        return self.ops.gat_bwd_exact_pre_table(g, aL, dY_rows, lse, Y, Ym, sma, self_col, side, heads=heads)
+
+    def gat_bwd_exact_gather_table(self, g, aR, X, dY, side, heads, slope, self_col):
+        """(dX, d_aR) from the gathered tables (gala_gat_bwd_exact_gather_ex_f32)."""
+        return self.ops.gat_bwd_exact_gather_table(g, aR, X, dY, side, self_col, heads=heads, slope=slope)
+
     def head_attn(self, X, w, b, heads):
         """[n, heads] per-head attention logits <X[:, head h], w_h> + b_h (gala_head_attn_f32)."""
         return self.ops.head_attn(X, w, b, heads=heads)
@@ -328,6 +341,31 @@ class CpuBackend:
                       dY.stride(0), F, heads, slope, _hp(lse), _hp(Y), Y.stride(0), _hp(Ym), Ym.stride(0), _hp(sma),
                       _hp(side), _hp(dX), dX.stride(0), _hp(d_aL), _hp(d_aR), None)
         return dX, d_aL, d_aR
+
+    def gat_stats_exact_table(self, g: CpuGraph, aL, aR, X, heads, slope, self_col, aR_out, wR=None, bR=None):
+        n, F = g.n_rows, X.shape[1]
+        Y, Ym = torch.empty((n, F)), torch.empty((n, F))
+        lse, sma = torch.empty(n * heads), torch.empty(n * heads)
+        _abi.call_cpu("gala_gat_fwd_stats_exact_ex_f32", g.csr(), _hp(aL), _hp(aR), _hp(wR), _hp(bR), _hp(X),
+                      X.stride(0), F, heads, slope, _hp(Y), F, _hp(lse), _hp(Ym), F, _hp(sma), _hp(self_col),
+                      _hp(aR_out), None)
+        return Y, lse, Ym, sma
+
+    def gat_bwd_exact_pre_table(self, g: CpuGraph, aL, dY_rows, lse, Y, Ym, sma, heads, self_col, side):
+        F = dY_rows.shape[1]
+        d_aL = torch.empty(g.n_rows * heads)
+        _abi.call_cpu("gala_gat_bwd_exact_pre_ex_f32", g.csr(), _hp(aL), _hp(dY_rows), dY_rows.stride(0), F, heads,
+                      _hp(lse), _hp(Y), Y.stride(0), _hp(Ym), Ym.stride(0), _hp(sma), _hp(self_col), _hp(side),
+                      _hp(d_aL), None)
+        return d_aL
+
+    def gat_bwd_exact_gather_table(self, g: CpuGraph, aR, X, dY, side, heads, slope, self_col):
+        F = dY.shape[1]
+        dX = torch.empty((g.n_rows, F), dtype=torch.float32)
+        d_aR = torch.empty(g.n_rows * heads)
+        _abi.call_cpu("gala_gat_bwd_exact_gather_ex_f32", g.csr(), _hp(aR), _hp(X), X.stride(0), _hp(dY), dY.stride(0),
+                      F, heads, slope, _hp(side), _hp(self_col), _hp(dX), dX.stride(0), _hp(d_aR), None)
+        return dX, d_aR
 
     def head_attn(self, X, w, b, heads):
         out = torch.empty((X.shape[0], heads), dtype=torch.float32)

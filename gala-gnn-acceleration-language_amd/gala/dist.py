@@ -629,6 +629,88 @@ class HaloGat:
         return self.part.halo_bytes(2 * self.F + self.H) if self.part.world > 1 else 0
 
 
+class HaloGatExact(HaloGat):
+    """The FIXED GAT layer (the stable softmax and its TRUE gradients) over a row partition with a
+    halo, computed exactly as one GPU computes it with gala_gat_{fwd,bwd}_stats_exact_f32.  The
+    whole graph's pattern must be symmetric (`symmetric`, the caller's statement about the WHOLE
+    graph: ValueError when false): every own row is stored whole, so own row c's column list is
+    the set of its in-edges (r, c), and dX[c], d_aR[c] are complete on c's owner -- no reverse
+    reduction.  Same partition, tables, exchange classes, self_col and hub-row plan
+    (part.split_threshold) as HaloGat; every row keeps its CSR edge order and the whole graph's
+    hub chunks, so every output is BIT-identical to the one-GPU pair.
+
+      forward_train(aL, aR, X[, wR, bR]) -> Y   (gala_gat_fwd_stats_exact_ex_f32; keeps aL, lse,
+                                                 Y, Ym, sma and the aR table for the backward)
+      backward(dY) -> (dX, d_aL, d_aR[, dwR, dbR])
+          1. the dY halo gather starts; 2. the pre-pass runs on the own rows (d_aL, and the side
+          lines {aL, lse, g, 0} into the side table's own block); 3. the side table's halo
+          gather starts (4 heads floats per row); 4. both are waited for; 5. the gather pass.
+          With wR (the source logit's per-head Linear, aR = X wR + bR) dX also takes d_aR wR
+          (gala_head_attn_bwd_f32) and (dwR, dbR) come from head_linear_grads fed d_aR -- which
+          is not d_aL here, unlike REF.
+
+    halo_bytes(): F + H floats per halo row forward (X, and a given aR; recomputed logits are
+    formed from the gathered X rows and send nothing, so the figure is then an upper bound by H),
+    F + 4H backward (dY and the side lines).  It is derived from the partition's row counts, not
+    measured: nothing here has run on more than one GPU."""
+
+    def __init__(self, part: GraphPartition, F: int, heads: int, backend, comm=None, slope: float = 0.2,
+                 symmetric: bool = False):
+        if not symmetric:
+            raise ValueError("HaloGatExact: the whole graph's pattern must be symmetric (row c's stored "
+                             "neighbours are then its in-edges); REF programs take HaloGat")
+        super().__init__(part, F, heads, backend, comm, slope)
+        if hasattr(self.graph, "hg") and part.split_threshold > 0:
+            # the host graph takes the whole graph's hub-row plan too (the kernels' association)
+            self.graph.set_split_plan(part.split_threshold)
+        self.Ss = backend.empty(part.n_cols, 4 * heads)
+        if part.halo_mode == "dense" and part.world > 1:
+            self.Ss.zero_()
+        # the side lines travel while the dY rows still do: an exchange (and send buffer) of their own
+        self.side_exchange = None
+        if comm is not None:
+            self.side_exchange = HaloExchange(part, comm, backend.device) if part.halo_mode == "p2p" else self.exchange
+
+    def forward_train(self, aL, aR, X, wR=None, bR=None):
+        n, H = self.part.n, self.H
+        self._wait(self._gather(self.Xs, X))
+        if aR is not None:
+            self._wait(self._gather(self.As, aR.reshape(n, H)))
+            out = self.be.gat_stats_exact_table(self.graph, aL, self.As, self.Xs, H, self.slope, self.self_col, None)
+        else:   # recomputed per edge from the gathered X rows; the own rows' logits into As
+            out = self.be.gat_stats_exact_table(self.graph, aL, None, self.Xs, H, self.slope, self.self_col, self.As,
+                                                wR=wR, bR=bR)
+        Y, lse, Ym, sma = out
+        self.saved = (aL, lse, Y, Ym, sma, wR, [])   # last: pending exchanges, as HaloGat keeps them (none)
+        return Y
+
+    def backward(self, dY):
+        if self.saved is None:
+            raise RuntimeError("HaloGatExact.backward: no forward_train to take the row statistics from")
+        aL, lse, Y, Ym, sma, wR, _ = self.saved
+        n, H = self.part.n, self.H
+        works = self._gather(self.dYs, dY)
+        # the rows' own dY: the caller's array, not the table's own block (which may start off the
+        # table's alignment when a row is no multiple of 16 bytes; one vector width serves a pass)
+        rows = dY if dY.data_ptr() % 16 == 0 else dY.clone()
+        d_aL = self.be.gat_bwd_exact_pre_table(self.graph, aL, rows, lse, Y, Ym, sma, H, self.self_col, self.Ss)
+        if self.side_exchange is not None:
+            works += [w for ws in self.side_exchange.start(self.Ss) for w in ws]
+        self._wait(works)
+        dX, d_aR = self.be.gat_bwd_exact_gather_table(self.graph, self.As, self.Xs, self.dYs, self.Ss, H, self.slope,
+                                                      self.self_col)
+        d_aL, d_aR = d_aL.view(n, H), d_aR.view(n, H)
+        if wR is None:
+            return dX, d_aL, d_aR
+        self.be.head_attn_bwd(d_aR, wR, H, dX)
+        dW, db = self.be.head_linear_grads(self.own_rows("X"), d_aR, H)
+        return dX, d_aL, d_aR, dW, db
+
+    def halo_bytes(self) -> int:
+        """Bytes this rank receives per forward + backward, from the partition's counts (derived)."""
+        return self.part.halo_bytes(2 * self.F + self.H + 4 * self.H) if self.part.world > 1 else 0
+
+
 class HaloGatOverlap(HaloGat):
     """HaloGat with the halo exchange hidden behind the edges already computable.  The
     forward runs the unnormalised row statistics of the edges into the rank's own columns

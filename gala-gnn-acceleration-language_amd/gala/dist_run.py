@@ -225,6 +225,39 @@ class _VcutGat(torch.autograd.Function):
         dX, d_aL = ctx.layer.backward(dy.contiguous())
         return d_aL, d_aL.clone(), dX, None
 
+
+class _ExactGatFfn(torch.autograd.Function):
+    """A FIXED GAT aggregation over a row partition (gala.dist.HaloGatExact) with the source logit
+    recomputed from x: inputs as _VcutGatFfn.  The true gradients: d_aL and d_aR are distinct, and
+    the attention Linear's dX term and (dW, db) come from d_aR (HaloGatExact.backward)."""
+
+    @staticmethod
+    def forward(ctx, aL, x, w, b, layer):
+        ctx.layer = layer
+        return layer.forward_train(aL.detach().contiguous(), None, x.detach().contiguous(),
+                                   w.detach().reshape(-1).contiguous(), b.detach().reshape(-1).contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        dX, d_aL, _, dW, db = ctx.layer.backward(dy.contiguous())
+        return d_aL, dX, dW.view(1, -1), db.view(-1), None
+
+
+class _ExactGat(torch.autograd.Function):
+    """A FIXED GAT aggregation over a row partition with a given source logit aR [n, H]: separate
+    d_aL and d_aR, the layer's true gradients."""
+
+    @staticmethod
+    def forward(ctx, aL, aR, x, layer):
+        ctx.layer = layer
+        return layer.forward_train(aL.detach().contiguous(), aR.detach().contiguous(), x.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        dX, d_aL, d_aR = ctx.layer.backward(dy.contiguous())
+        return d_aL, d_aR, dX, None
+
+
 class _GatInputLayer(torch.autograd.Function):
     """A GAT program's first layer in input space over ranks (gala.dist.HaloGatInput): the FFN of
     the dataset's features, its two attention Linears and the REF aggregation (optionally the
@@ -359,6 +392,12 @@ def _gat_in_tmode(n_rows: int) -> bool:
     return n_rows * 896 * 4 <= float(os.environ.get("GALA_GAT_IN_T_MAX_GB", "64")) * (1 << 30)
 
 
+def gat_exact_enabled() -> bool:
+    """GALA_DIST_GAT_EXACT=1 runs FIXED GAT programs (gala.dist.HaloGatExact).  Off by default:
+    without it a FIXED program is refused, as before the exact pair ran over a partition."""
+    return os.environ.get("GALA_DIST_GAT_EXACT", "") == "1"
+
+
 def check_program(ir: dict, layout_mode: str = "halo") -> None:
     """Raise NotImplementedError when this runtime cannot run the (post-pass) program on the
     given layout; the message names what is missing."""
@@ -369,7 +408,21 @@ def check_program(ir: dict, layout_mode: str = "halo") -> None:
     s = ir["sched"]
     if "GAT_AGGREGATE" in ops:
         if s.get("gat_mode", 0) != 0:
-            raise NotImplementedError("gala.dist_run: FIXED-mode GAT (its backward needs A^T)")
+            # FIXED: the exact pair over the row partition (gala.dist.HaloGatExact), whose
+            # regrouping needs every own row whole and the whole pattern symmetric
+            if not gat_exact_enabled():
+                raise NotImplementedError("gala.dist_run: FIXED-mode GAT is off by default; GALA_DIST_GAT_EXACT=1 "
+                                          "runs an undirected program on --layout halo with its true gradients "
+                                          "(the whole graph's pattern must be symmetric)")
+            if layout_mode == "vcut":
+                raise NotImplementedError("gala.dist_run: FIXED-mode GAT on the vertex cut (the cut splits rows: "
+                                          "a row's in-edges are no longer its own column list); use --layout halo")
+            if not s["undirected"]:
+                raise NotImplementedError("gala.dist_run: directed FIXED-mode GAT programs (the exact backward "
+                                          "takes row c's stored neighbours as its in-edges: a symmetric pattern)")
+            if s["kernel_sample"]:
+                raise NotImplementedError("gala.dist_run: kernel-sampled FIXED-mode GAT programs (the row "
+                                          "statistics are sums over all of a row's edges)")
         if not s["undirected"]:
             # the reference's directed REF backward applies the forward-order alpha to the
             # transposed pattern's edge positions (common.h:835-894 on slot 2g+1): every rank
@@ -418,6 +471,11 @@ class Program:
         self._in_layers = {v: m for v, m in self._in_plan.items() if input_layer_eligible(
             ir, by_out[v], self._in_plan, layout_mode, self.part, symmetric)}
         self._in_skip = {u for m in self._in_layers.values() for u in (m["ffn"], m["attn"], m["relu"]) if u is not None}
+        # FIXED programs: every GAT layer through HaloGatExact, on a symmetric whole graph only
+        self.gat_exact = s.get("gat_mode", 0) != 0 and any(nd["op"] == "GAT_AGGREGATE" for nd in ir["nodes"])
+        if self.gat_exact and not symmetric():
+            raise NotImplementedError("gala.dist_run: FIXED-mode GAT on a graph whose pattern is not symmetric "
+                                      "(the exact backward takes row c's stored neighbours as its in-edges)")
         self.keep_gat_out = False    # --dump: keep the first training forward's GAT layer outputs
         self.gat_out = {}
         # the aggregation pair (forward, slot 2g+1 backward) of every graph g of the program
@@ -487,6 +545,10 @@ class Program:
         from . import vertex_cut as vc
         key = nd["out"]
         if key not in self._gat:
+            if self.gat_exact:   # check_program: the halo layout, undirected, not kernel-sampled
+                self._gat[key] = gdist.HaloGatExact(self.part, F, H, self.be, self.comm, slope=float(nd["param"]),
+                                                    symmetric=True)
+                return self._gat[key]
             cls = vc.VertexCutGat if self.layout == "vcut" else gdist.HaloGat
             self._gat[key] = cls(self.part, F, H, self.be, self.comm, slope=float(nd["param"]))
         return self._gat[key]
@@ -521,7 +583,7 @@ class Program:
                     moved = layer.halo_bytes()
                 else:   # VertexCutGat: 2F + 2H floats per sent partial row forward, F backward
                     moved = layer.part.comm_bytes(3 * layer.F + 2 * layer.H) if self.world > 1 else 0
-                out.append({"node": nd["out"], "kind": "input" if inp else "stats",
+                out.append({"node": nd["out"], "kind": "input" if inp else ("exact" if self.gat_exact else "stats"),
                             "tmode": bool(inp and layer.tmode), "halo_bytes_per_step": int(moved),
                             "setup_bytes": int(layer.setup_bytes()) if inp else 0})
         return out
@@ -590,11 +652,12 @@ class Program:
                 n = x.shape[0]
                 H = aL.numel() // max(n, 1)
                 layer = self._gat_layer(nd, x.shape[1], H)
+                ffn_op, op_ = (_ExactGatFfn, _ExactGat) if self.gat_exact else (_VcutGatFfn, _VcutGat)
                 if nd["weight"]:     # gat_aggregate_ffn: attnR = the Linear of x, recomputed
                     m = self.modules[nd["weight"]]
-                    y = _VcutGatFfn.apply(aL.reshape(n, H), x, m.weight, m.bias, layer)
+                    y = ffn_op.apply(aL.reshape(n, H), x, m.weight, m.bias, layer)
                 else:
-                    y = _VcutGat.apply(aL.reshape(n, H), a[1].reshape(n, H), x, layer)
+                    y = op_.apply(aL.reshape(n, H), a[1].reshape(n, H), x, layer)
                 if self.keep_gat_out and torch.is_grad_enabled() and out not in self.gat_out:
                     self.gat_out[out] = y.detach()
             elif op == "FFN":

@@ -528,6 +528,42 @@ def gat_bwd_stats_exact(g: DeviceGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads=1,
     return dX, d_aL, d_aR
 
 
+def gat_stats_exact_table(g: DeviceGraph, aL, X, self_col, aR=None, wR=None, bR=None, aR_out=None, heads=1, slope=0.2):
+    """gala_gat_fwd_stats_exact_ex_f32: the exact forward of g's rows over gathered tables (X
+    [n_cols, F]; aR [n_cols, heads], or aR None and the own columns' recomputed logits written
+    into the caller's column-indexed aR_out); self_col int32 [rows].  Returns (Y, lse, Ym, sma)."""
+    F = X.shape[1]
+    Y, Ym = _rows_like(X, g.n_rows), _rows_like(X, g.n_rows)
+    lse = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32)
+    sma = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32)
+    _abi.call("gala_gat_fwd_stats_exact_ex_f32", g.csr(2 * ((F + 3) // 4 * 4) + 3 * heads), _dp(aL), _dp(aR),
+              _dp(wR), _dp(bR), _dp(X), X.stride(0), F, heads, slope, _dp(Y), Y.stride(0), _dp(lse), _dp(Ym),
+              Ym.stride(0), _dp(sma), _dp(self_col), _dp(aR_out), _stream())
+    return Y, lse, Ym, sma
+
+
+def gat_bwd_exact_pre_table(g: DeviceGraph, aL, dY_rows, lse, Y, Ym, sma, self_col, side, heads=1):
+    """gala_gat_bwd_exact_pre_ex_f32: d_aL of g's rows, and their side lines {aL, lse, g, 0}
+    written into the column-indexed table `side` [n_cols, heads, 4] at self_col."""
+    F = dY_rows.shape[1]
+    d_aL = torch.empty(g.n_rows * heads, device=dY_rows.device, dtype=torch.float32)
+    _abi.call("gala_gat_bwd_exact_pre_ex_f32", g.csr(), _dp(aL), _dp(dY_rows), dY_rows.stride(0), F, heads, _dp(lse),
+              _dp(Y), Y.stride(0), _dp(Ym), Ym.stride(0), _dp(sma), _dp(self_col), _dp(side), _dp(d_aL), _stream())
+    return d_aL
+
+
+def gat_bwd_exact_gather_table(g: DeviceGraph, aR, X, dY, side, self_col, heads=1, slope=0.2):
+    """gala_gat_bwd_exact_gather_ex_f32: (dX, d_aR) of g's rows from the gathered tables aR, X,
+    dY and the completed side table (the whole graph's pattern symmetric: the caller's assertion)."""
+    F = dY.shape[1]
+    dX = _rows_like(dY, g.n_rows)
+    d_aR = torch.empty(g.n_rows * heads, device=dY.device, dtype=torch.float32)
+    _abi.call("gala_gat_bwd_exact_gather_ex_f32", g.csr(2 * ((F + 3) // 4 * 4) + heads), _dp(aR), _dp(X), X.stride(0),
+              _dp(dY), dY.stride(0), F, heads, slope, _dp(side), _dp(self_col), _dp(dX), dX.stride(0), _dp(d_aR),
+              _stream())
+    return dX, d_aR
+
+
 def head_attn(X, w, b=None, heads=1):
     """gala_head_attn_f32: out[r, h] = <X[r, head h], w[head h]> + b[h] ([N, heads])."""
     N, F = X.shape

@@ -111,6 +111,20 @@ int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const
                                      float slope, const float *lse, const float *Y, int64_t ldy,
                                      const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
                                      int64_t lddx, float *d_aL, float *d_aR, void *stream);
+/* the exact pair over gathered tables (gala_gat_fwd_stats_exact_ex_f32 and the backward's two
+ * passes); the square twins above are these at self_col NULL */
+int gala_cpu_gat_fwd_stats_exact_ex_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
+                                        const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
+                                        float slope, float *Y, int64_t ldy, float *lse, float *Ym, int64_t ldym,
+                                        float *sma, const int32_t *self_col, float *aR_out, void *stream);
+int gala_cpu_gat_bwd_exact_pre_ex_f32(const gala_csr_t *A, const float *aL, const float *dY_rows, int64_t lddy,
+                                      int32_t F, int32_t heads, const float *lse, const float *Y, int64_t ldy,
+                                      const float *Ym, int64_t ldym, const float *sma, const int32_t *self_col,
+                                      float *side, float *d_aL, void *stream);
+int gala_cpu_gat_bwd_exact_gather_ex_f32(const gala_csr_t *A, const float *aR, const float *X, int64_t ldx,
+                                         const float *dY, int64_t lddy, int32_t F, int32_t heads, float slope,
+                                         const float *side, const int32_t *self_col, float *dX, int64_t lddx,
+                                         float *d_aR, void *stream);
 int gala_cpu_gat_fwd_stats_ex_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
                                   const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
                                   float slope, float *Y, int64_t ldy, float *q_out, float *Ym, int64_t ldym,

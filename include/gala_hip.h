@@ -479,6 +479,44 @@ int gala_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const flo
                                  const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
                                  int64_t lddx, float *d_aL, float *d_aR, void *stream);
 /*
+ * The exact pair over gathered tables (a row partition's halo, gala/dist.py HaloGatExact): a
+ * rectangular pattern (n_rows <= n_cols) whose columns index tables of n_cols rows; the WHOLE
+ * graph's pattern is symmetric and every own row is stored whole, so own row c's column list is
+ * the set of its in-edges and dX[c], d_aR[c] are complete on c's owner.  self_col[r] is the
+ * table column of row r's own vertex (NULL: r itself, square pattern only).
+ *   gala_gat_fwd_stats_exact_ex_f32: X ([n_cols, F]) and a given aR ([n_cols, heads]) are read by
+ *     column; aR_out (aR NULL) is column-indexed and written at the own columns self_col[r]
+ *     from X[self_col[r]]; Y, lse, Ym, sma are row-indexed.
+ *   gala_gat_bwd_exact_pre_ex_f32: the row-local pre-pass.  dY_rows (row r at dY_rows + r*lddy),
+ *     Y, Ym, sma, lse, aL row-indexed; writes d_aL [n_rows, heads] and row r's side line
+ *     {aL, lse, g, 0} into the column-indexed side table [n_cols, heads, 4] at self_col[r].
+ *   gala_gat_bwd_exact_gather_ex_f32: the gather pass over a completed side table (the halo rows'
+ *     lines copied in by the caller: 16 bytes per head and halo row).  Row r with s = self_col[r]
+ *     takes aR[s]; its edges read dY[c] (nontemporal) and side[c] by column; the store reads
+ *     X[s] and writes dX[r], d_aR[r] row-indexed.
+ * gala_gat_{fwd,bwd}_stats_exact_f32 are these paths at self_col NULL (the backward: the
+ * pre-pass, then the gather, with one vector width for both), bit for bit.  Hub rows, their
+ * workspace (the gather: 2F + heads floats per chunk; the pre-pass reads no plan) and the shape
+ * limits are the square pair's.  One pass picks one vector width for every operand it reads:
+ * dY_rows and the dY table too, so the own block of a table whose rows are no multiple of 16
+ * bytes may start off the table's alignment.  GALA_ERR_INVALID_ARG, nothing launched:
+ * n_rows > n_cols; self_col NULL on a pattern that is not square; side NULL or not 16-byte
+ * aligned.  Results equal the square pair's on the same rows bit for bit when the operands'
+ * strides and alignment give the same vector width.
+ */
+int gala_gat_fwd_stats_exact_ex_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
+                                    const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
+                                    float slope, float *Y, int64_t ldy, float *lse, float *Ym, int64_t ldym,
+                                    float *sma, const int32_t *self_col, float *aR_out, void *stream);
+int gala_gat_bwd_exact_pre_ex_f32(const gala_csr_t *A, const float *aL, const float *dY_rows, int64_t lddy,
+                                  int32_t F, int32_t heads, const float *lse, const float *Y, int64_t ldy,
+                                  const float *Ym, int64_t ldym, const float *sma, const int32_t *self_col,
+                                  float *side, float *d_aL, void *stream);
+int gala_gat_bwd_exact_gather_ex_f32(const gala_csr_t *A, const float *aR, const float *X, int64_t ldx,
+                                     const float *dY, int64_t lddy, int32_t F, int32_t heads, float slope,
+                                     const float *side, const int32_t *self_col, float *dX, int64_t lddx,
+                                     float *d_aR, void *stream);
+/*
  * The same pair over a gathered feature table (a row partition's halo, gala/dist.py
  * HaloGat): the pattern's columns index the table (n_cols >= n_rows), so a row is no longer
  * its own column.  gala_gat_fwd_stats_ex_f32: self_col[r] = the table column of row r's own
