@@ -1371,6 +1371,74 @@ extern "C" int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float
     return GALA_OK;
 }
 
+// the directed backward: the pre-pass over A's rows, the gather pass over AT (its plan's chunks)
+extern "C" int gala_cpu_gat_bwd_stats_exact_t_f32(const gala_csr_t *A, const gala_csr_t *AT, const float *aL,
+                                                  const float *aR, const float *X, int64_t ldx, const float *dY,
+                                                  int64_t lddy, int32_t F, int32_t heads, float slope,
+                                                  const float *lse, const float *Y, int64_t ldy, const float *Ym,
+                                                  int64_t ldym, const float *sma, float *side, float *dX,
+                                                  int64_t lddx, float *d_aL, float *d_aR, void *) {
+    int st = check_csr(A);
+    if (st) return st;
+    if ((st = check_csr(AT))) return st;
+    if (heads < 1) return GALA_ERR_INVALID_ARG;
+    if (A->n_seg != 1 || AT->n_seg != 1) return GALA_ERR_INVALID_ARG;
+    if (A->n_cols != A->n_rows || AT->n_cols != AT->n_rows || AT->n_rows != A->n_rows || AT->nnz != A->nnz)
+        return GALA_ERR_INVALID_ARG;
+    if (F < 1 || F % heads != 0 || ldx < F || lddy < F || ldy < F || ldym < F || lddx < F)
+        return GALA_ERR_INVALID_ARG;
+    if (A->n_rows == 0) return GALA_OK;
+    if (!side || ((uintptr_t)side % 16) != 0) return GALA_ERR_INVALID_ARG;
+    if (!aL || !aR || !X || !dY || !lse || !Y || !Ym || !sma || !dX || !d_aL || !d_aR) return GALA_ERR_INVALID_ARG;
+    ExactShape sh;
+    if ((st = exact_shape(F, heads, {ldx, lddy, ldy, ldym, lddx}, &sh))) return st;
+    exact_pre_pass(A, sh, aL, dY, lddy, F, heads, lse, Y, ldy, Ym, ldym, sma, nullptr, side, d_aL);
+    exact_gather_pass(AT, sh, aR, X, ldx, dY, lddy, F, heads, slope, side, nullptr, dX, lddx, d_aR);
+    return GALA_OK;
+}
+
+// gala_csr_is_transpose_i32's tests, item for item; result: a host int32
+extern "C" int gala_cpu_csr_is_transpose_i32(const gala_csr_t *a, const gala_csr_t *at, int32_t *result, void *) {
+    int st = check_csr(a);
+    if (st) return st;
+    if ((st = check_csr(at))) return st;
+    if (!result) return GALA_ERR_INVALID_ARG;
+    if (a->n_seg != 1 || at->n_seg != 1) return GALA_ERR_INVALID_ARG;
+    if (a->n_rows != a->n_cols || at->n_rows != at->n_cols || a->n_rows != at->n_rows) return GALA_ERR_INVALID_ARG;
+    *result = 0;
+    const int64_t n = a->n_rows;
+    if (n == 0) return GALA_OK;
+    auto off = [](int32_t v, int64_t nnz) { return v < 0 ? (int64_t)0 : std::min<int64_t>(v, nnz); };
+    // edge e of row `row`: column in range and above its predecessor's in the row
+    auto ascends = [&](const gala_csr_t *g, int64_t row, int64_t e) {
+        const int32_t c = g->col[e];
+        if (c < 0 || c >= n) return false;
+        return e <= off(g->rowptr[row], g->nnz) || g->col[e - 1] < c;
+    };
+    int64_t bad = 0;
+    const int32_t *trp = at->rowptr;
+    bad += !(trp[0] == 0 && trp[n] == at->nnz && a->nnz == at->nnz && trp[0] <= trp[1]);
+    for (int64_t c = 1; c < n; ++c) bad += !(trp[c] <= trp[c + 1]);
+    // the row of edge e as the kernel's search finds it: the last r with rowptr[r] <= e
+    auto edge_row = [&](const int32_t *rp, int64_t e) {
+        return std::max<int64_t>(std::upper_bound(rp + 1, rp + n, (int32_t)e) - rp - 1, 0);
+    };
+    for (int64_t e = 0; e < at->nnz; ++e) bad += !ascends(at, edge_row(trp, e), e);
+    for (int64_t e = 0; e < a->nnz; ++e) {
+        const int64_t r = edge_row(a->rowptr, e);
+        if (!ascends(a, r, e)) {
+            ++bad;
+            continue;
+        }
+        const int64_t c = a->col[e];
+        const int32_t *lo = at->col + off(trp[c], at->nnz), *hi = at->col + off(trp[c + 1], at->nnz);
+        const int32_t *p = lo < hi ? std::lower_bound(lo, hi, (int32_t)r) : hi;
+        bad += !(p < hi && *p == r);
+    }
+    *result = (int32_t)std::min<int64_t>(bad, INT32_MAX);
+    return GALA_OK;
+}
+
 extern "C" int gala_cpu_head_attn_f32(int64_t n_rows, int32_t F, int32_t heads, const float *X, int64_t ldx,
                                       const float *w, const float *b, float *out, void *) {
     if (n_rows < 0 || F < 1 || heads < 1 || F % heads != 0 || ldx < F) return GALA_ERR_INVALID_ARG;

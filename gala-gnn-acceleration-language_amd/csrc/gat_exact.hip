@@ -16,6 +16,11 @@
 // Both sums aL[r] + aR[c] have the same operands in the two passes, so an edge's LeakyReLU
 // branch is the same in both.  Every sum is sequential in CSR order (hub rows: per-chunk
 // partials added in ascending chunk order from the plan's workspace); no atomics.
+//
+// Directed pattern (gala_gat_bwd_stats_exact_t_f32): the in-edges of c are row c of A^T, so
+// the same gather kernels walk A^T (its own hub plan and workspace) after the pre-pass over
+// A's rows; gala_csr_is_transpose_i32 (csr_check.hip) is the test that the second pattern is
+// the first one's transpose.
 #include "gat_common.h"
 
 namespace gala {
@@ -559,6 +564,13 @@ int exact_vec(const ExactArgs &a, int L, int ch, int heads, int hw) {
     return GALA_OK;
 }
 
+// a graph with hub rows brings the workspace their chunk partials need
+bool plan_ws_short(const gala_csr_t *A, int64_t ws_need) {
+    const gala_split_plan_t *plan = A->split;
+    return ws_need > 0 && plan && plan->n_chunks > 0 && plan->n_rows_split > 0 && A->n_seg == 1 &&
+           (!plan->workspace || plan->ws_cols < ws_need);
+}
+
 // The shape checks and the launch: nothing is launched unless every check passed.
 int exact_dispatch(const gala_csr_t *A, ExactArgs &a, int F, int heads, int vec, bool rc, int64_t ws_need) {
     const int D = F / heads;
@@ -567,11 +579,7 @@ int exact_dispatch(const gala_csr_t *A, ExactArgs &a, int F, int heads, int vec,
     const int hw = (D % vec == 0) ? D / vec : 0;
     if (L > 64) return GALA_ERR_UNSUPPORTED;
     if (heads > 1 && (hw == 0 || (hw & (hw - 1)))) return GALA_ERR_UNSUPPORTED;
-    // a graph with hub rows brings the workspace their chunk partials need
-    const gala_split_plan_t *plan = A->split;
-    if (ws_need > 0 && plan && plan->n_chunks > 0 && plan->n_rows_split > 0 && A->n_seg == 1 &&
-        (!plan->workspace || plan->ws_cols < ws_need))
-        return GALA_ERR_INVALID_ARG;
+    if (plan_ws_short(A, ws_need)) return GALA_ERR_INVALID_ARG;
     a.split = ws_need > 0 && hub_split(A, ws_need, &a.sp);
     int r;
     if (rc && a.bwd) return GALA_ERR_INVALID_ARG;  // the backward reads aR: it has no recompute
@@ -645,11 +653,20 @@ struct ExactBwd {
     float *side, *dX, *d_aL, *d_aR;
 };
 
-int exact_backward(const gala_csr_t *A, const ExactBwd &b, int32_t F, int32_t heads, float slope, bool pre,
-                   bool gather, void *stream) {
+// AT (NULL: A itself) is the pattern the gather pass walks, A's transpose: row c of AT lists
+// the rows r with an edge (r, c) of A.  The pre-pass is row-local and takes of A its n_rows.
+int exact_backward(const gala_csr_t *A, const gala_csr_t *AT, const ExactBwd &b, int32_t F, int32_t heads,
+                   float slope, bool pre, bool gather, void *stream) {
     ExactArgs a{};
     int st = edge_setup(A, heads, &a.p);
     if (st) return st;
+    EdgeParams pt{};
+    if (AT) {
+        if ((st = edge_setup(AT, heads, &pt))) return st;
+        if (A->n_seg != 1 || AT->n_seg != 1) return GALA_ERR_INVALID_ARG;
+        if (A->n_cols != A->n_rows || AT->n_cols != AT->n_rows || AT->n_rows != A->n_rows || AT->nnz != A->nnz)
+            return GALA_ERR_INVALID_ARG;
+    }
     if (F < 1 || F % heads != 0 || b.lddy < F) return GALA_ERR_INVALID_ARG;
     if (pre && (b.ldy < F || b.ldym < F)) return GALA_ERR_INVALID_ARG;
     if (gather && (b.ldx < F || b.lddx < F)) return GALA_ERR_INVALID_ARG;
@@ -684,7 +701,20 @@ int exact_backward(const gala_csr_t *A, const ExactBwd &b, int32_t F, int32_t he
     a.hs = (hipStream_t)stream;
     a.bwd = true, a.pre = pre, a.gather = gather;
     // the pre-pass is row-local: no hub chunks, no workspace
-    return exact_dispatch(A, a, F, heads, vec, false, gather ? 2 * (int64_t)F + heads : 0);
+    const int64_t ws_need = gather ? 2 * (int64_t)F + heads : 0;
+    if (!AT) return exact_dispatch(A, a, F, heads, vec, false, ws_need);
+    // the two passes apart, each over its own pattern, with the one vector width; AT's plan is
+    // looked at before the pre-pass goes out, so a short workspace launches nothing.  "Nothing is
+    // launched unless every check passed" rests on the two dispatches below sharing F, heads and
+    // vec: the shape checks of exact_dispatch then give the same answer for both, and the one
+    // check that reads the pattern (the plan's workspace) is this line.  A check added to
+    // exact_dispatch that can differ between A and AT must be made here too, before the pre-pass
+    if (plan_ws_short(AT, ws_need)) return GALA_ERR_INVALID_ARG;
+    ExactArgs g = a;
+    g.p = pt, g.pre = false;
+    a.gather = false;
+    if ((st = exact_dispatch(A, a, F, heads, vec, false, 0))) return st;
+    return exact_dispatch(AT, g, F, heads, vec, false, ws_need);
 }
 
 }  // namespace
@@ -698,7 +728,21 @@ extern "C" int gala_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL
     b.aL = aL, b.aR = aR, b.X = X, b.dY = dY, b.dY_rows = dY, b.lse = lse, b.Y = Y, b.Ym = Ym, b.sma = sma;
     b.ldx = ldx, b.lddy = lddy, b.ldy = ldy, b.ldym = ldym, b.lddx = lddx;
     b.side = side, b.dX = dX, b.d_aL = d_aL, b.d_aR = d_aR;
-    return exact_backward(A, b, F, heads, slope, true, true, stream);
+    return exact_backward(A, nullptr, b, F, heads, slope, true, true, stream);
+}
+
+extern "C" int gala_gat_bwd_stats_exact_t_f32(const gala_csr_t *A, const gala_csr_t *AT, const float *aL,
+                                              const float *aR, const float *X, int64_t ldx, const float *dY,
+                                              int64_t lddy, int32_t F, int32_t heads, float slope, const float *lse,
+                                              const float *Y, int64_t ldy, const float *Ym, int64_t ldym,
+                                              const float *sma, float *side, float *dX, int64_t lddx, float *d_aL,
+                                              float *d_aR, void *stream) {
+    if (!AT) return GALA_ERR_INVALID_ARG;
+    ExactBwd b{};
+    b.aL = aL, b.aR = aR, b.X = X, b.dY = dY, b.dY_rows = dY, b.lse = lse, b.Y = Y, b.Ym = Ym, b.sma = sma;
+    b.ldx = ldx, b.lddy = lddy, b.ldy = ldy, b.ldym = ldym, b.lddx = lddx;
+    b.side = side, b.dX = dX, b.d_aL = d_aL, b.d_aR = d_aR;
+    return exact_backward(A, AT, b, F, heads, slope, true, true, stream);
 }
 
 extern "C" int gala_gat_bwd_exact_pre_ex_f32(const gala_csr_t *A, const float *aL, const float *dY_rows, int64_t lddy,
@@ -708,7 +752,7 @@ extern "C" int gala_gat_bwd_exact_pre_ex_f32(const gala_csr_t *A, const float *a
     ExactBwd b{};
     b.aL = aL, b.dY_rows = dY_rows, b.lse = lse, b.Y = Y, b.Ym = Ym, b.sma = sma;
     b.lddy = lddy, b.ldy = ldy, b.ldym = ldym, b.self_col = self_col, b.side = side, b.d_aL = d_aL;
-    return exact_backward(A, b, F, heads, 0.0f, true, false, stream);
+    return exact_backward(A, nullptr, b, F, heads, 0.0f, true, false, stream);
 }
 
 extern "C" int gala_gat_bwd_exact_gather_ex_f32(const gala_csr_t *A, const float *aR, const float *X, int64_t ldx,
@@ -718,5 +762,5 @@ extern "C" int gala_gat_bwd_exact_gather_ex_f32(const gala_csr_t *A, const float
     ExactBwd b{};
     b.aR = aR, b.X = X, b.dY = dY, b.ldx = ldx, b.lddy = lddy, b.lddx = lddx, b.self_col = self_col;
     b.side = const_cast<float *>(side), b.dX = dX, b.d_aR = d_aR;
-    return exact_backward(A, b, F, heads, slope, false, true, stream);
+    return exact_backward(A, nullptr, b, F, heads, slope, false, true, stream);
 }

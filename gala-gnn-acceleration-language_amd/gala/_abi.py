@@ -124,6 +124,9 @@ SIGNATURES = {
                                                     _P, _I64, _P, _P, _P]),
     "gala_gat_bwd_stats_exact_f32": (ctypes.c_int, [_CSR, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _F, _P, _P, _I64,
                                                     _P, _I64, _P, _P, _P, _I64, _P, _P, _P]),
+    "gala_gat_bwd_stats_exact_t_f32": (ctypes.c_int, [_CSR, _CSR, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _F, _P, _P,
+                                                      _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P]),
+    "gala_csr_is_transpose_i32": (ctypes.c_int, [_CSR, _CSR, _P, _P]),
     "gala_gat_fwd_stats_exact_ex_f32": (ctypes.c_int, [_CSR, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _P, _I64,
                                                        _P, _P, _I64, _P, _P, _P, _P]),
     "gala_gat_bwd_exact_pre_ex_f32": (ctypes.c_int, [_CSR, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _I64, _P,
@@ -245,7 +248,8 @@ CPU_OPS = ("gala_spmm_f32", "gala_spmm_ex_f32", "gala_row_broadcast_deg_f32", "g
            "gala_gat_fwd_stats_ex_f32", "gala_gat_bwd_stats_ex_f32", "gala_gat_fwd_partial_stats_ex_f32",
            "gala_gat_fwd_continue_f32", "gala_gat_bwd_stats_linear_f32", "gala_gat_fwd_stats_exact_f32",
            "gala_gat_bwd_stats_exact_f32", "gala_gat_fwd_stats_exact_ex_f32", "gala_gat_bwd_exact_pre_ex_f32",
-           "gala_gat_bwd_exact_gather_ex_f32", "gala_head_attn_f32",
+           "gala_gat_bwd_exact_gather_ex_f32", "gala_gat_bwd_stats_exact_t_f32", "gala_csr_is_transpose_i32",
+           "gala_head_attn_f32",
            "gala_head_attn_bwd_f32", "gala_edge_permute_f32", "gala_dense_grad_workspace",
            "gala_dense_grad_f32", "gala_gat_in_prep_f32", "gala_gat_in_fwd_f32", "gala_gat_in_bwd_workspace",
            "gala_gat_in_bwd_f32", "gala_gat_in_fwd_rect_f32", "gala_gat_in_bwd_rect_f32",

@@ -88,6 +88,17 @@ class HipBackend:
         return self.ops.gat_bwd_stats_exact(g, aL, aR, X, dY, lse, Y, Ym, sma, heads=heads, slope=slope,
                                             symmetric=symmetric)
 
+    def is_transpose(self, g, gT) -> bool:
+        """Whether gT's pattern is g's transposed (gala_csr_is_transpose_i32)."""
+        return self.ops.is_transpose(g, gT)
+
+    def gat_bwd_stats_exact_t(self, g, gT, aL, aR, X, dY, lse, Y, Ym, sma, heads, slope):
+        """(dX, d_aL, d_aR) on a directed pattern g, the gather pass over its transpose gT
+        (gala_gat_bwd_stats_exact_t_f32); gT is tested once per pair."""
+        if not self.ops.pair_cached(g, gT, lambda: self.is_transpose(g, gT)):
+            raise ValueError("gat_bwd_stats_exact_t: gT is not the transpose of g")
+        return self.ops.gat_bwd_stats_exact_t(g, gT, aL, aR, X, dY, lse, Y, Ym, sma, heads=heads, slope=slope)
+
     def gat_stats_exact_table(self, g, aL, aR, X, heads, slope, self_col, aR_out, wR=None, bR=None):
         """(Y, lse, Ym, sma) of the exact forward over gathered tables (gala_gat_fwd_stats_exact_ex_f32)."""
         return self.ops.gat_stats_exact_table(g, aL, X, self_col, aR=aR, wR=wR, bR=bR, aR_out=aR_out, heads=heads,
@@ -340,6 +351,25 @@ class CpuBackend:
         _abi.call_cpu("gala_gat_bwd_stats_exact_f32", g.csr(), _hp(aL), _hp(aR), _hp(X), X.stride(0), _hp(dY),
                       dY.stride(0), F, heads, slope, _hp(lse), _hp(Y), Y.stride(0), _hp(Ym), Ym.stride(0), _hp(sma),
                       _hp(side), _hp(dX), dX.stride(0), _hp(d_aL), _hp(d_aR), None)
+        return dX, d_aL, d_aR
+
+    def is_transpose(self, g: CpuGraph, gT: CpuGraph) -> bool:
+        if g.hg.n_seg != 1 or gT.hg.n_seg != 1 or not (g.n_rows == g.n_cols == gT.n_rows == gT.n_cols):
+            return False
+        count = ctypes.c_int32(-1)
+        _abi.call_cpu("gala_csr_is_transpose_i32", g.csr(), gT.csr(), ctypes.addressof(count), None)
+        return count.value == 0
+
+    def gat_bwd_stats_exact_t(self, g: CpuGraph, gT: CpuGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads, slope):
+        from . import ops
+        if not ops.pair_cached(g, gT, lambda: self.is_transpose(g, gT)):
+            raise ValueError("gat_bwd_stats_exact_t: gT is not the transpose of g")
+        n, F = g.n_rows, dY.shape[1]
+        dX = torch.empty((n, F), dtype=torch.float32)
+        d_aL, d_aR, side = torch.empty(n * heads), torch.empty(n * heads), torch.empty(n * heads * 4)
+        _abi.call_cpu("gala_gat_bwd_stats_exact_t_f32", g.csr(), gT.csr(), _hp(aL), _hp(aR), _hp(X), X.stride(0),
+                      _hp(dY), dY.stride(0), F, heads, slope, _hp(lse), _hp(Y), Y.stride(0), _hp(Ym), Ym.stride(0),
+                      _hp(sma), _hp(side), _hp(dX), dX.stride(0), _hp(d_aL), _hp(d_aR), None)
         return dX, d_aL, d_aR
 
     def gat_stats_exact_table(self, g: CpuGraph, aL, aR, X, heads, slope, self_col, aR_out, wR=None, bR=None):

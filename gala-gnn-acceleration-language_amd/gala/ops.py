@@ -8,6 +8,7 @@ wrappers and autograd Functions of codegen/gala.cu) lives in host/gala_torch.cpp
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -524,6 +525,59 @@ def gat_bwd_stats_exact(g: DeviceGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads=1,
     side = torch.empty(g.n_rows * heads * 4, device=dY.device, dtype=torch.float32)
     _abi.call("gala_gat_bwd_stats_exact_f32", g.csr(2 * ((F + 3) // 4 * 4) + heads), _dp(aL), _dp(aR), _dp(X),
               X.stride(0), _dp(dY), dY.stride(0), F, heads, slope, _dp(lse), _dp(Y), Y.stride(0), _dp(Ym),
+              Ym.stride(0), _dp(sma), _dp(side), _dp(dX), dX.stride(0), _dp(d_aL), _dp(d_aR), _stream())
+    return dX, d_aL, d_aR
+
+
+def pair_cached(g, gT, test) -> bool:
+    """test() once per (g, gT) pair of graph objects; the answer is kept on g while gT lives
+    (entries of dead gT objects are dropped at the next miss).  Shared with gala.backend; not
+    an operator."""
+    seen = g.__dict__.setdefault("_transpose_pairs", {})
+    hit = seen.get(id(gT))
+    if hit is None or hit[0]() is not gT:
+        for k in [k for k, (ref, _) in seen.items() if ref() is None]:
+            del seen[k]
+        hit = (weakref.ref(gT), bool(test()))
+        seen[id(gT)] = hit
+    return hit[1]
+
+
+def is_transpose(g: DeviceGraph, gT: DeviceGraph) -> bool:
+    """Whether gT's pattern is exactly the transpose of g's (gala_csr_is_transpose_i32: one pass
+    over the edges on the device, no host transpose).  Patterns that are not square,
+    single-segment and of one n are no pair: False."""
+    if g.n_seg != 1 or gT.n_seg != 1 or not (g.n_rows == g.n_cols == gT.n_rows == gT.n_cols):
+        return False
+    count = torch.empty(1, device=g.col.device, dtype=torch.int32)
+    _abi.call("gala_csr_is_transpose_i32", g.csr(), gT.csr(), _dp(count), _stream())
+    return int(count.item()) == 0
+
+
+def gat_exact_directed(g: DeviceGraph, gT: DeviceGraph, aL, X, dY, aR=None, wR=None, bR=None, heads=1, slope=0.2):
+    """The stable-softmax layer and its true gradients on a directed pattern g with its
+    transpose gT: gala_gat_fwd_stats_exact_f32 on g, then gala_gat_bwd_stats_exact_t_f32, whose
+    gather pass walks gT (c's in-edges).  Returns ((Y, lse, Ym, sma, aR), (dX, d_aL, d_aR)), what
+    gat_fwd_stats_exact and gat_bwd_stats_exact return.  gT is tested once per (g, gT) pair
+    (is_transpose, kept on the pair); a gT that is not g's transpose raises ValueError before a
+    launch of the layer."""
+    if not pair_cached(g, gT, lambda: is_transpose(g, gT)):
+        raise ValueError("gat_exact_directed: gT is not the transpose of g")
+    fwd = gat_fwd_stats_exact(g, aL, X, aR=aR, wR=wR, bR=bR, heads=heads, slope=slope)
+    Y, lse, Ym, sma, ar = fwd
+    return fwd, gat_bwd_stats_exact_t(g, gT, aL, ar, X, dY, lse, Y, Ym, sma, heads=heads, slope=slope)
+
+
+def gat_bwd_stats_exact_t(g: DeviceGraph, gT: DeviceGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads=1, slope=0.2):
+    """gala_gat_bwd_stats_exact_t_f32: (dX, d_aL, d_aR) from the forward's row statistics on g, the
+    gather pass over gT -- g's transpose, the caller's assertion (gat_exact_directed tests it)."""
+    F = dY.shape[1]
+    dX = _rows_like(dY, g.n_rows)
+    d_aL = torch.empty(g.n_rows * heads, device=dY.device, dtype=torch.float32)
+    d_aR = torch.empty(g.n_rows * heads, device=dY.device, dtype=torch.float32)
+    side = torch.empty(g.n_rows * heads * 4, device=dY.device, dtype=torch.float32)
+    _abi.call("gala_gat_bwd_stats_exact_t_f32", g.csr(), gT.csr(2 * ((F + 3) // 4 * 4) + heads), _dp(aL), _dp(aR),
+              _dp(X), X.stride(0), _dp(dY), dY.stride(0), F, heads, slope, _dp(lse), _dp(Y), Y.stride(0), _dp(Ym),
               Ym.stride(0), _dp(sma), _dp(side), _dp(dX), dX.stride(0), _dp(d_aL), _dp(d_aR), _stream())
     return dX, d_aL, d_aR
 

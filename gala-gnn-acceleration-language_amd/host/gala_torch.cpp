@@ -44,6 +44,8 @@ struct Backend {
     decltype(&gala_gat_bwd_stats_linear_f32) gat_bwd_stats_linear;
     decltype(&gala_gat_fwd_stats_exact_f32) gat_fwd_stats_exact;
     decltype(&gala_gat_bwd_stats_exact_f32) gat_bwd_stats_exact;
+    decltype(&gala_gat_bwd_stats_exact_t_f32) gat_bwd_stats_exact_t;
+    decltype(&gala_csr_is_transpose_i32) csr_is_transpose;
     decltype(&gala_head_attn_f32) head_attn;
     decltype(&gala_head_attn_bwd_f32) head_attn_bwd;
     decltype(&gala_edge_permute_f32) permute;
@@ -65,6 +67,7 @@ const Backend kHip{gala_spmm_ex_f32, gala_degree_f32, gala_row_broadcast_f32,
                    gala_gat_fwd_ex_f32, gala_gat_bwd_ex_f32, gala_gat_bwd_fused_f32,
                    gala_gat_fwd_stats_f32, gala_gat_bwd_stats_f32, gala_gat_bwd_stats_linear_f32,
                    gala_gat_fwd_stats_exact_f32, gala_gat_bwd_stats_exact_f32,
+                   gala_gat_bwd_stats_exact_t_f32, gala_csr_is_transpose_i32,
                    gala_head_attn_f32, gala_head_attn_bwd_f32,
                    gala_edge_permute_f32, gala_dense_grad_workspace, gala_dense_grad_f32,
                    gala_gat_in_prep_f32, gala_gat_in_fwd_f32, gala_gat_in_bwd_workspace, gala_gat_in_bwd_f32,
@@ -78,6 +81,7 @@ const Backend kCpu{gala_cpu_spmm_ex_f32, gala_cpu_degree_f32, gala_cpu_row_broad
                    gala_cpu_gat_fwd_ex_f32, gala_cpu_gat_bwd_ex_f32, gala_cpu_gat_bwd_fused_f32,
                    gala_cpu_gat_fwd_stats_f32, gala_cpu_gat_bwd_stats_f32, gala_cpu_gat_bwd_stats_linear_f32,
                    gala_cpu_gat_fwd_stats_exact_f32, gala_cpu_gat_bwd_stats_exact_f32,
+                   gala_cpu_gat_bwd_stats_exact_t_f32, gala_cpu_csr_is_transpose_i32,
                    gala_cpu_head_attn_f32, gala_cpu_head_attn_bwd_f32,
                    gala_cpu_edge_permute_f32, gala_cpu_dense_grad_workspace,
                    gala_cpu_dense_grad_f32, gala_cpu_gat_in_prep_f32, gala_cpu_gat_in_fwd_f32,
@@ -476,6 +480,7 @@ int GraphSlots::push(torch::Tensor offsets, torch::Tensor cols, torch::Tensor va
     merged.push_back(mg);
     pattern_t.push_back(nullptr);
     holds_previous.push_back(-1);
+    transposes_previous.push_back(-1);
     if (offset_graph.size() == 1) nrows = offsets.numel() / segs - 1;
     return (int)offset_graph.size() - 1;
 }
@@ -1073,6 +1078,36 @@ bool exact_stats_layer(int64_t li, int64_t x_rows) {
     return transposed_pattern(2 * li).symmetric;  // tested once, kept with the slot
 }
 
+// The directed pair (GALA_GAT_EXACT_DIRECTED=1, off by default; read per layer call like the
+// switch above): the exact forward on slot 2li and gala_gat_bwd_stats_exact_t_f32, whose gather
+// pass walks slot 2li+1, for a FIXED layer whose two slots are distinct, single-segment,
+// square, unweighted and unsampled -- once gala_csr_is_transpose_i32 has found slot 2li+1 to
+// be slot 2li's transpose (one pass over the edges on the device, once per pair of slots; no
+// host transpose).
+bool exact_directed_enabled() {
+    const char *e = std::getenv("GALA_GAT_EXACT_DIRECTED");
+    return e && e[0] == '1';
+}
+
+bool exact_directed_layer(int64_t li, int64_t x_rows) {
+    if (!exact_directed_enabled()) return false;
+    Slot fw = slot(2 * li), bw = slot(2 * li + 1);
+    auto &S = global_slots();
+    if (fw.segs != 1 || bw.segs != 1 || fw.weighted || bw.weighted || S.nsamples != 0) return false;
+    if (fw.off.numel() - 1 != x_rows || bw.off.numel() != fw.off.numel()) return false;
+    if (same_pattern(fw, bw) || fw.off.device() != bw.off.device()) return false;
+    int8_t &tr = S.transposes_previous[2 * li + 1];
+    if (tr < 0) {
+        CsrView a = view(fw.off, fw.cols, nullptr, fw.bounds, fw.segs);
+        CsrView t = view(bw.off, bw.cols, nullptr, bw.bounds, bw.segs);
+        auto count = torch::empty({1}, torch::TensorOptions().dtype(torch::kInt).device(fw.off.device()));
+        check(be(fw.off).csr_is_transpose(&a.c, &t.c, count.data_ptr<int32_t>(), stream_of(fw.off)),
+              "gala_csr_is_transpose_i32");
+        tr = count.item<int32_t>() == 0;
+    }
+    return tr;
+}
+
 struct GatExact {
     torch::Tensor Y, lse, Ym, sma, aR;  // aR: the given logits, or the kernel's recompute
 };
@@ -1101,18 +1136,35 @@ bool gat_forward_exact(const Slot &s, const torch::Tensor &l, const torch::Tenso
 }
 
 // The exact backward: dX, d_aL and d_aR (distinct) from the forward's rows.
+// directed: the gather pass over slot 2li+1, the forward pattern's transpose (its own plan).
 bool gat_backward_exact(const torch::Tensor &l, const GatExact &o, const torch::Tensor &x,
-                        const torch::Tensor &dY_in, int64_t li, double slope, int heads, GatGrads &g) {
+                        const torch::Tensor &dY_in, int64_t li, double slope, int heads, GatGrads &g,
+                        bool directed = false) {
     Slot fw = slot(2 * li);
     const torch::Tensor dY = heads == 1 ? pad_rows4(dY_in) : dY_in.contiguous();
     const int64_t F = o.Y.size(1), nrows = fw.off.numel() / fw.segs - 1;
     CsrView cf = view(fw.off, fw.cols, nullptr, fw.bounds, fw.segs);
     cf.c.n_cols = dY.size(0);
-    with_workspace(cf, fw.off, 2 * ((F + 3) / 4 * 4) + heads);  // hub rows: {dX, dXm, sg}
+    if (!directed) with_workspace(cf, fw.off, 2 * ((F + 3) / 4 * 4) + heads);  // hub rows: {dX, dXm, sg}
     check_on(dY, fw.off, "grad");
     auto dX = rows_like(dY, nrows);
     auto daL = torch::empty_like(l), daR = torch::empty_like(l);
     auto side = torch::empty({nrows * heads * 4}, fopts(x));   // {aL, lse, g, 0} per (row, head)
+    if (directed) {
+        Slot bw = slot(2 * li + 1);
+        CsrView ct = view(bw.off, bw.cols, nullptr, bw.bounds, bw.segs);
+        with_workspace(ct, bw.off, 2 * ((F + 3) / 4 * 4) + heads);  // hub rows of A^T: {dX, dXm, sg}
+        const int st = be(fw.off).gat_bwd_stats_exact_t(
+            &cf.c, &ct.c, l.data_ptr<float>(), o.aR.data_ptr<float>(), x.data_ptr<float>(), x.stride(0),
+            dY.data_ptr<float>(), dY.stride(0), (int32_t)F, heads, (float)slope, o.lse.data_ptr<float>(),
+            o.Y.data_ptr<float>(), o.Y.stride(0), o.Ym.data_ptr<float>(), o.Ym.stride(0), o.sma.data_ptr<float>(),
+            side.data_ptr<float>(), dX.data_ptr<float>(), dX.stride(0), daL.data_ptr<float>(), daR.data_ptr<float>(),
+            stream_of(fw.off));
+        if (st == GALA_ERR_UNSUPPORTED) return false;
+        check(st, "gala_gat_bwd_stats_exact_t_f32");
+        g = {daL, daR, dX};
+        return true;
+    }
     const int st = be(fw.off).gat_bwd_stats_exact(
         &cf.c, l.data_ptr<float>(), o.aR.data_ptr<float>(), x.data_ptr<float>(), x.stride(0), dY.data_ptr<float>(),
         dY.stride(0), (int32_t)F, heads, (float)slope, o.lse.data_ptr<float>(), o.Y.data_ptr<float>(), o.Y.stride(0),
@@ -1153,9 +1205,13 @@ struct GatAggregate : public torch::autograd::Function<GatAggregate> {
         // the statistics only serve a backward: none without gradients (eval forwards)
         const bool grad = ctx->needs_input_grad(0) || ctx->needs_input_grad(1) || ctx->needs_input_grad(2);
         GatExact ex;
-        if (mode == GALA_SOFTMAX_FIXED && grad && exact_stats_layer(li, x.size(0)) &&
+        const bool fixed_grad = mode == GALA_SOFTMAX_FIXED && grad;
+        const bool symm = fixed_grad && exact_stats_layer(li, x.size(0));
+        const bool directed = fixed_grad && !symm && exact_directed_layer(li, x.size(0));
+        if ((symm || directed) &&
             gat_forward_exact(s, l, r, x, {}, {}, heads, slope, ex)) {
             ctx->saved_data["exact"] = true;
+            if (directed) ctx->saved_data["exact_t"] = true;
             ctx->save_for_backward({l, r, x, ex.lse, ex.Y, ex.Ym, ex.sma});
             return ex.Y;
         }
@@ -1181,7 +1237,8 @@ struct GatAggregate : public torch::autograd::Function<GatAggregate> {
         GatGrads g;
         if (ctx->saved_data.count("exact")) {
             const GatExact ex{sv[4], sv[3], sv[5], sv[6], r};
-            if (!gat_backward_exact(l, ex, x, grad_outputs[0], li, slope, heads, g)) {
+            if (!gat_backward_exact(l, ex, x, grad_outputs[0], li, slope, heads, g,
+                                    ctx->saved_data.count("exact_t") > 0)) {
                 auto alpha = torch::empty({slot(2 * li).cols.numel() * heads}, fopts(x));  // rebuild alpha
                 gat_forward_launch(slot(2 * li), l, r, x, {}, {}, heads, slope, mode, alpha.data_ptr<float>(), nullptr);
                 g = gat_backward(l, r, x, alpha, {}, grad_outputs[0], li, slope, mode, heads, {}, {});
@@ -1255,10 +1312,14 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
         const bool grad = ctx->needs_input_grad(0) || ctx->needs_input_grad(1) || ctx->needs_input_grad(2) ||
                           ctx->needs_input_grad(3);
         GatExact ex;
-        if (mode == GALA_SOFTMAX_FIXED && grad && exact_stats_layer(li, x.size(0)) &&
+        const bool fixed_grad = mode == GALA_SOFTMAX_FIXED && grad;
+        const bool symm = fixed_grad && exact_stats_layer(li, x.size(0));
+        const bool directed = fixed_grad && !symm && exact_directed_layer(li, x.size(0));
+        if ((symm || directed) &&
             gat_forward_exact(s, l, {}, x, w, b, heads, slope, ex)) {
             // ex.aR: the recomputed source logits, the backward's second operand of every logit
             ctx->saved_data["exact"] = true;
+            if (directed) ctx->saved_data["exact_t"] = true;
             ctx->save_for_backward({l, x, w, b_saved, ex.aR, ex.lse, ex.Y, ex.Ym, ex.sma});
             return ex.Y;
         }
@@ -1291,7 +1352,8 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
         bool done = false, fused_linear = false;
         if (exact) {
             const GatExact ex{sv[6], sv[5], sv[7], sv[8], sv[4]};
-            done = gat_backward_exact(l, ex, x, grad_outputs[0], li, slope, heads, g);
+            done = gat_backward_exact(l, ex, x, grad_outputs[0], li, slope, heads, g,
+                                      ctx->saved_data.count("exact_t") > 0);
             alpha = torch::empty({0}, fopts(x));
             if (!done) {  // rebuild alpha for the alpha-storing backward
                 alpha = torch::empty({slot(2 * li).cols.numel() * heads}, fopts(x));

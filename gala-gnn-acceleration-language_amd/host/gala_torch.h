@@ -83,6 +83,8 @@ struct GraphSlots {
     // slot i holds slot i-1's pattern, element for element (-1: not compared yet).  Slots are only
     // appended until clear(), so the answer stays with the index
     std::vector<int8_t> holds_previous;
+    // slot i holds the transpose of slot i-1's pattern (gala_csr_is_transpose_i32; -1: not tested yet)
+    std::vector<int8_t> transposes_previous;
     int64_t nrows = 0;
     int ra = 5, rb = 7;    // kernel-sampling coefficients (common.h:813-833)
     int nsamples = 0;      // 0 = no kernel sampling

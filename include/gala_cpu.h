@@ -111,6 +111,14 @@ int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const
                                      float slope, const float *lse, const float *Y, int64_t ldy,
                                      const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
                                      int64_t lddx, float *d_aL, float *d_aR, void *stream);
+/* the directed backward (the pre-pass over A's rows, the gather pass over AT with AT's plan) and
+ * the transpose test (result: a host int32; the kernel's tests item for item) */
+int gala_cpu_gat_bwd_stats_exact_t_f32(const gala_csr_t *A, const gala_csr_t *AT, const float *aL, const float *aR,
+                                       const float *X, int64_t ldx, const float *dY, int64_t lddy, int32_t F,
+                                       int32_t heads, float slope, const float *lse, const float *Y, int64_t ldy,
+                                       const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
+                                       int64_t lddx, float *d_aL, float *d_aR, void *stream);
+int gala_cpu_csr_is_transpose_i32(const gala_csr_t *a, const gala_csr_t *at, int32_t *result, void *stream);
 /* the exact pair over gathered tables (gala_gat_fwd_stats_exact_ex_f32 and the backward's two
  * passes); the square twins above are these at self_col NULL */
 int gala_cpu_gat_fwd_stats_exact_ex_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,

@@ -479,6 +479,33 @@ int gala_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const flo
                                  const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
                                  int64_t lddx, float *d_aL, float *d_aR, void *stream);
 /*
+ * The exact backward on a directed pattern: the forward is gala_gat_fwd_stats_exact_f32 on A,
+ * and AT is A's transpose (row c of AT lists, ascending, the rows r with an edge (r, c) of A;
+ * the caller asserts it -- gala_csr_is_transpose_i32 tests it).  The pre-pass runs over A's n
+ * rows, then the gather pass of gala_gat_bwd_stats_exact_f32 walks AT: row c's stored
+ * neighbours are then c's in-edges, whatever A's symmetry.  Hub rows of AT go through AT's own
+ * plan and workspace (2F + heads floats per chunk; A's plan is not read).  Both patterns are
+ * square, single-segment, of the same n and nnz, else GALA_ERR_INVALID_ARG; so is an AT plan
+ * with hub rows and a missing or smaller workspace; nothing is launched then.  With AT == A
+ * (a symmetric pattern) the results are gala_gat_bwd_stats_exact_f32's bit for bit.
+ */
+int gala_gat_bwd_stats_exact_t_f32(const gala_csr_t *A, const gala_csr_t *AT, const float *aL, const float *aR,
+                                   const float *X, int64_t ldx, const float *dY, int64_t lddy, int32_t F,
+                                   int32_t heads, float slope, const float *lse, const float *Y, int64_t ldy,
+                                   const float *Ym, int64_t ldym, const float *sma, float *side, float *dX,
+                                   int64_t lddx, float *d_aL, float *d_aR, void *stream);
+/*
+ * Is `at` exactly the transpose of `a`?  Both square, single-segment, of the same n (else
+ * GALA_ERR_INVALID_ARG).  result: one int32 in device memory, set to the number of failed
+ * tests (a thread's share is capped, so it is a lower bound past 2^31 / grid failures); zero
+ * means transpose.  Tested on the device in one grid-stride pass, stream-ordered: the nnz are
+ * equal; at's row offsets start at 0, end at nnz and do not descend; every row of at and of a
+ * has in-range, strictly ascending columns; every edge (r, c) of a is found by binary search
+ * for r in row c of at.  A malformed `at` (offsets or columns out of range) is counted, never
+ * followed.  The values and plans of both are ignored.
+ */
+int gala_csr_is_transpose_i32(const gala_csr_t *a, const gala_csr_t *at, int32_t *result, void *stream);
+/*
  * The exact pair over gathered tables (a row partition's halo, gala/dist.py HaloGatExact): a
  * rectangular pattern (n_rows <= n_cols) whose columns index tables of n_cols rows; the WHOLE
  * graph's pattern is symmetric and every own row is stored whole, so own row c's column list is
