@@ -1091,6 +1091,9 @@ static int gat_bwd_impl(const gala_csr_t *A, const float *aL, const float *aR, c
     if (!aL || (!aR && !wR) || !dY || !d_aL || (A->nnz > 0 && (!X || !alpha)))
         return GALA_ERR_INVALID_ARG;
     if (mode == GALA_SOFTMAX_FIXED && !d_logit && A->nnz > 0) return GALA_ERR_INVALID_ARG;
+    // the REF kernels form the row sums of dz in one pass and never dz per edge: a buffer handed
+    // in would come back unwritten
+    if (mode == GALA_SOFTMAX_REF && d_logit) return GALA_ERR_UNSUPPORTED;
     if (!aR && mode != GALA_SOFTMAX_REF) return GALA_ERR_UNSUPPORTED;
     if (q && mode != GALA_SOFTMAX_REF) return GALA_ERR_INVALID_ARG;
     const int D = F / heads;

@@ -326,7 +326,10 @@ def gat_bwd_attn(g: DeviceGraph, aL, wR, bR, X, dY, alpha, slope=0.2):
 
 def gat_bwd(g: DeviceGraph, aL, aR, X, dY, alpha, heads=1, slope=0.2, mode=_abi.GALA_SOFTMAX_REF,
             want_dz=False):
-    """Fused GAT edge backward (gala_gat_bwd_f32): returns (d_aL, dz or None)."""
+    """Fused GAT edge backward (gala_gat_bwd_f32): returns (d_aL, dz or None).  dz per edge is
+    FIXED mode's output (the REF kernels form its row sums only): want_dz in REF mode raises."""
+    if want_dz and mode != _abi.GALA_SOFTMAX_FIXED:
+        raise ValueError("gat_bwd: dz per edge is formed in GALA_SOFTMAX_FIXED mode only")
     F = X.shape[1]
     d_aL = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32)
     dz = (torch.empty(g.nnz * heads, device=X.device, dtype=torch.float32)
@@ -356,7 +359,10 @@ def gat_fwd_ex(g: DeviceGraph, aL, X, aR=None, wR=None, bR=None, heads=1, slope=
 
 def gat_bwd_ex(g: DeviceGraph, aL, X, dY, alpha, q=None, aR=None, wR=None, bR=None, heads=1, slope=0.2,
                mode=_abi.GALA_SOFTMAX_REF, want_dz=False):
-    """gala_gat_bwd_ex_f32: (d_aL, dz or None); q given: alpha holds p (alpha = p * q)."""
+    """gala_gat_bwd_ex_f32: (d_aL, dz or None); q given: alpha holds p (alpha = p * q).  want_dz in
+    REF mode raises (see gat_bwd)."""
+    if want_dz and mode != _abi.GALA_SOFTMAX_FIXED:
+        raise ValueError("gat_bwd_ex: dz per edge is formed in GALA_SOFTMAX_FIXED mode only")
     F = X.shape[1]
     d_aL = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32)
     dz = (torch.empty(g.nnz * heads, device=X.device, dtype=torch.float32)

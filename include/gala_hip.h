@@ -328,9 +328,11 @@ int gala_gat_fwd_f32(const gala_csr_t *A, const float *aL, const float *aR, cons
  *   acc = S*eps + sum_row sds;  ds = sds - alpha*acc;
  *   dz = ds if aL[row,h]+aR[col,h] > 0 else ds*slope       (LeakyReLU backward);
  *   d_aL[row,h] = S*eps + sum_row dz                         (eps = 1e-12 REF, 0 FIXED).
- * d_logit (nullable in REF mode, required in FIXED mode) receives dz per (edge, head);
- * REF mode computes the row sum of dz as sum(m*sds) - acc*sum(m*alpha), m the LeakyReLU
- * slope factor, in the same single pass.  Replaces the backward chain edge_sddmm ->
+ * d_logit (required in FIXED mode, NULL in REF mode) receives dz per (edge, head) in FIXED
+ * mode; REF mode computes the row sum of dz as sum(m*sds) - acc*sum(m*alpha), m the LeakyReLU
+ * slope factor, in the same single pass and never forms dz per edge: a non-NULL d_logit in
+ * REF mode is GALA_ERR_UNSUPPORTED, before any launch (gala_gat_bwd_ex_f32 likewise; the host
+ * twins of include/gala_cpu.h do write it in REF mode).  Replaces the backward chain edge_sddmm ->
  * softmax backward -> LeakyReLU backward -> node_spmv_backward_of_sddmm
  * (cuda.h:505-524,808-845; common.h:622-675,791-799,835-894) in one kernel.  Requires
  * heads | 64 and D/VEC a power of two when heads > 1 (else GALA_ERR_UNSUPPORTED).

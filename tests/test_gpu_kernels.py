@@ -1195,3 +1195,45 @@ def test_gat_bwd_stats_linear_bitexact(F, heads, split):
     dX1, daL1 = ops.gat_bwd_stats(dg, aL, aR, dY, q, Y, Ym, sma, heads=heads, wR=wR)
     assert torch.equal(daL1, daL0)
     assert torch.equal(dX1, dX0)
+
+
+@pytest.mark.parametrize("ex", [False, True])
+def test_gat_bwd_ref_mode_refuses_a_dz_buffer(ex):
+    """The REF backward kernels form the row sums of dz in one pass and never dz per edge
+    (csrc/gat.hip): a d_logit buffer in REF mode is GALA_ERR_UNSUPPORTED before any launch -- it
+    used to come back unwritten with GALA_OK -- and the wrappers refuse want_dz there; FIXED mode
+    writes every element."""
+    g = cora_like()
+    dg = ops.DeviceGraph.from_host(g, split=False)
+    F, H = 32, 4
+    aL, aR = dev(features(g.n_rows, H, seed=1)), dev(features(g.n_cols, H, seed=2))
+    X, dY = dev(features(g.n_cols, F, seed=3)), dev(features(g.n_rows, F, seed=4))
+    _, al = ops.gat_fwd(dg, aL, aR, X, heads=H, want_alpha=True)
+    dz = torch.full((g.nnz * H,), float("nan"), device=DEV)
+    daL = torch.empty(g.n_rows * H, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(mode, d_logit):
+        head = (dg.csr(3 * H), aL.data_ptr(), aR.data_ptr())
+        tail = (X.data_ptr(), X.stride(0), dY.data_ptr(), dY.stride(0), F, H, 0.2, mode, al.data_ptr())
+        if ex:
+            _abi.call("gala_gat_bwd_ex_f32", *head, None, None, *tail, None, d_logit, daL.data_ptr(), stream)
+        else:
+            _abi.call("gala_gat_bwd_f32", *head, *tail, d_logit, daL.data_ptr(), stream)
+    with pytest.raises(_abi.GalaError) as e:
+        call(_abi.GALA_SOFTMAX_REF, dz.data_ptr())
+    assert e.value.status == _abi.GALA_ERR_UNSUPPORTED
+    call(_abi.GALA_SOFTMAX_REF, None)
+    ref = daL.clone()
+    assert bool(torch.isfinite(ref).all())
+    fn = ops.gat_bwd_ex if ex else ops.gat_bwd
+    args = (dg, aL, X, dY, al) if ex else (dg, aL, aR, X, dY, al)
+    kw = dict(aR=aR) if ex else {}
+    with pytest.raises(ValueError, match="FIXED"):
+        fn(*args, heads=H, want_dz=True, **kw)
+    got, none = fn(*args, heads=H, **kw)
+    assert none is None and torch.equal(got, ref)
+    _, alf = ops.gat_fwd(dg, aL, aR, X, heads=H, mode=_abi.GALA_SOFTMAX_FIXED, want_alpha=True)
+    al = alf
+    call(_abi.GALA_SOFTMAX_FIXED, dz.data_ptr())
+    assert not bool(torch.isnan(dz).any())
