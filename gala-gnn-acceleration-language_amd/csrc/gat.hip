@@ -5,6 +5,7 @@
 // Replaces the torch compositions around the emitted GAT kernels
 // (src/codegen/common.h:622-675, 735-810, 835-894; cuda.h:505-524, 679-734, 808-845).
 #include "gat_common.h"
+#include "gat_wide.h"
 
 namespace gala {
 
@@ -910,6 +911,9 @@ static int gat_fwd_impl(const gala_csr_t *A, const float *aL, const float *aR, c
     const int64_t ws_need = stats ? 2 * (int64_t)F + 3 * heads : (int64_t)F + 2 * heads;
     a.split = (!alpha_out || G % heads == 0) && hub_split(A, ws_need, &a.sp);
     const bool rc = aR == nullptr;
+    // rows past 64 float4 vectors: the wide-row kernels (gat_wide.hip), ahead of the ladder
+    if (gat_wide_shape(A, F, heads, vec) && !partial && !init_acc && !self_col)
+        return gat_wide_fwd(a.p, a.d, a.mode, a.hs);
     // alpha of heads that do not divide the row group is formed by a per-head pass that
     // re-reads aR: there is none to read when it is recomputed
     if (rc && alpha_out && G % heads != 0) return GALA_ERR_UNSUPPORTED;

@@ -913,6 +913,17 @@ GatGrads gat_backward(const torch::Tensor &l, torch::Tensor r, const torch::Tens
     return {daL, daR, dX};
 }
 
+// HIP backend only: past 256 floats per row only the row-statistics pair has a backward there
+// (gala_gat_bwd_ex_f32, gala_gat_bwd_fused_f32 and gala_sddmm_dot_f32 stay at 256), so a layer
+// on the device that needs gradients and did not take the pair is refused in its forward,
+// before any work, not in its backward.  The host-CPU backend has no width limit in these.
+void check_wide_has_backward(bool grad, const torch::Tensor &x) {
+    const int64_t F = x.size(1);
+    TORCH_CHECK(!grad || !x.is_cuda() || F <= 256, "gala: GAT layer failed: ",
+                gala_status_string(GALA_ERR_UNSUPPORTED),
+                " (rows of ", F, " floats have a backward only as a REF layer on one pattern without hub rows)");
+}
+
 // One launch of the fused GAT forward (gala_gat_fwd_ex_f32) on slot 2li: aR, or its
 // per-head recompute from x (wR, bR).  alpha / q as the entry point documents.
 torch::Tensor gat_forward_launch(const Slot &s, const torch::Tensor &l, const torch::Tensor &r,
@@ -1220,6 +1231,7 @@ struct GatAggregate : public torch::autograd::Function<GatAggregate> {
             ctx->save_for_backward({l, r, x, o.q, o.Y, o.Ym, o.sma, o.p});
             return o.Y;
         }
+        check_wide_has_backward(grad, x);
         auto alpha = recompute ? torch::empty({0}, fopts(x)) : torch::empty({s.cols.numel() * heads}, fopts(x));
         auto q = factored ? torch::empty({nrows * heads}, fopts(x)) : torch::empty({0}, fopts(x));
         auto Y = gat_forward_launch(s, l, r, x, {}, {}, heads, slope, mode,
@@ -1329,6 +1341,7 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
             ctx->save_for_backward({l, x, w, b_saved, o.aR, o.q, o.Y, o.Ym, o.sma, o.p});
             return o.Y;
         }
+        check_wide_has_backward(grad, x);
         auto alpha = recompute ? torch::empty({0}, fopts(x)) : torch::empty({s.cols.numel() * heads}, fopts(x));
         auto q = factored ? torch::empty({nrows * heads}, fopts(x)) : torch::empty({0}, fopts(x));
         auto Y = gat_forward_launch(s, l, {}, x, w, b, heads, slope, mode,

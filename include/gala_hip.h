@@ -317,6 +317,10 @@ int gala_edge_softmax_bwd_f32(const gala_csr_t *A, const float *alpha, const flo
  * alpha_out (nullable) receives alpha for the backward pass.
  * Replaces the forward chain edge_sddvv -> LeakyReLU -> softmax autograd -> weighted
  * aggregate_node_mul_sum_call (common.h:622-894).
+ * Row widths: up to 64 vectors per row (F <= 256 with float4 operands); WIDE ROWS,
+ * 256 < F <= 1024, are served (csrc/gat_wide.hip) when D = F/heads is a multiple of 4,
+ * heads <= 32, X / Y and their leading dimensions are 16-byte aligned, A is one segment and
+ * its plan has no hub rows; anything else past 64 vectors is GALA_ERR_UNSUPPORTED.
  */
 int gala_gat_fwd_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *X,
                      int64_t ldx, int32_t F, int32_t heads, float slope, int32_t mode, float *Y,
@@ -374,6 +378,9 @@ int gala_gat_bwd_attn_f32(const gala_csr_t *A, const float *aL, const float *wR,
  * Several heads need D = F/heads a multiple of the vector width with D/VEC a power of two
  * for the recompute (else GALA_ERR_UNSUPPORTED).  Replaces the same chains as
  * gala_gat_fwd_f32 / gala_gat_bwd_f32.
+ * Wide rows (256 < F <= 1024, the conditions at gala_gat_fwd_f32): the forward serves aR and
+ * its recompute for any such D, alpha and the factored (p, q), REF and FIXED -- but not
+ * GALA_GAT_PARTIAL; gala_gat_bwd_ex_f32 stays at 64 vectors per row.
  */
 /* mode flag of gala_gat_fwd_ex_f32 (REF only, q_out required, alpha_out NULL): a PARTIAL
  * forward over one column range of the graph -- Y[r] = sum_e p_e X[col_e] unnormalised and
@@ -438,6 +445,13 @@ int gala_gat_bwd_fused_f32(const gala_csr_t *A, const float *aL, const float *aR
  * aL + aR)), 1e12) * q) from aR, or fl(p * q) when the forward's p is given (aR may then be
  * NULL)) and d_aL[r,h] = (<dY,Ym>_h - (S*eps + <dY,Y>_h) *
  * sma[r,h]) + S*eps (= d_aR in REF mode), eps = 1e-12.
+ * Wide rows (256 < F <= 1024, the conditions at gala_gat_fwd_f32, every operand row 16-byte
+ * aligned): both functions serve them for any D that is a multiple of 4 -- the forward with
+ * aR or its recompute, aR_out and p_out, the backward from aR or from p.  Y, q, Ym, sma and dX
+ * with given aR equal the narrow kernels' bit for bit on a 256-float column block of whole
+ * heads.  gala_gat_bwd_stats_linear_f32 serves them too without dY_rows (the Linear's term is
+ * added at the dX store as on narrow rows); the _ex / _partial / _continue forms stay at 64
+ * vectors per row.
  */
 int gala_gat_fwd_stats_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
                            const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
