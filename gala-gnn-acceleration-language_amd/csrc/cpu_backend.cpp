@@ -1042,9 +1042,21 @@ extern "C" int gala_cpu_gat_bwd_stats_linear_f32(const gala_csr_t *A, const floa
 namespace {
 
 // The kernels' row layout: vectors of `vec` floats, `hw` lanes per head, `ch` vectors per lane.
+// Wide rows (256 < F <= 1024, gat_exact_wide.hip): a head's dot is summed in `ng` aligned groups
+// of hw lanes (one float4 each), the group sums added in order; `u` edges per batch.
 struct ExactShape {
     int vec, hw, ch;
+    int ng = 1, u = 8;
+    bool wide = false;
 };
+
+// the wide kernels' further conditions: whole calls on one square segment without hub rows
+int exact_wide_ok(const ExactShape &sh, const gala_csr_t *A, const gala_csr_t *AT, bool whole) {
+    if (!sh.wide) return GALA_OK;
+    for (const gala_csr_t *g : {A, AT})
+        if (g && (g->n_seg != 1 || (g->split && g->split->n_rows_split > 0))) return GALA_ERR_UNSUPPORTED;
+    return whole ? GALA_OK : GALA_ERR_UNSUPPORTED;
+}
 
 // vec from the row strides as the kernels pick it (the pointers are taken as aligned)
 int exact_shape(int32_t F, int32_t H, std::initializer_list<int64_t> lds, ExactShape *sh) {
@@ -1060,6 +1072,12 @@ int exact_shape(int32_t F, int32_t H, std::initializer_list<int64_t> lds, ExactS
     };
     while (vec > 1 && !ok(vec)) vec >>= 1;
     const int L = (F + vec - 1) / vec;
+    if (vec == 4 && F > 256 && F <= 1024 && H <= 32 && D % 4 == 0) {
+        int g0 = 1;
+        while (g0 < 64 && (D / 4) % (2 * g0) == 0) g0 *= 2;
+        *sh = ExactShape{4, g0, 1, D / 4 / g0, F <= 512 ? 8 : 4, true};
+        return GALA_OK;
+    }
     if (L > 64) return GALA_ERR_UNSUPPORTED;
     const int ch = (H == 1 && vec < 4 && L > 16) ? (L + 15) / 16 : 1;
     int G = 16;
@@ -1075,6 +1093,14 @@ int exact_shape(int32_t F, int32_t H, std::initializer_list<int64_t> lds, ExactS
 
 // <a, b> over one head's n elements: lane l's fma chain over its vectors, then the xor butterfly
 float exact_lane_dot(const float *a, const float *b, int n, const ExactShape &sh) {
+    if (sh.wide) {  // the head's ng groups of hw float4 lanes, their sums added in order
+        ExactShape grp = sh;
+        grp.wide = false;
+        const int gn = 4 * sh.hw;
+        float s = exact_lane_dot(a, b, gn, grp);
+        for (int g = 1; g < sh.ng; ++g) s = s + exact_lane_dot(a + g * gn, b + g * gn, gn, grp);
+        return s;
+    }
     float v[64];
     for (int l = 0; l < sh.hw; ++l) {
         float s = 0.0f;
@@ -1111,7 +1137,7 @@ void exact_row_pieces(const gala_csr_t *A, int64_t r, Fn &&f) {
     }
 }
 
-constexpr int kExactU = 8;  // edges per batch (one max rescale each)
+constexpr int kExactU = 8;  // edges per batch at most (one max rescale each): ExactShape::u
 
 }  // namespace
 
@@ -1135,6 +1161,7 @@ extern "C" int gala_cpu_gat_fwd_stats_exact_ex_f32(const gala_csr_t *A, const fl
     if (aR_out && aR) return GALA_ERR_INVALID_ARG;
     ExactShape sh;
     if ((st = exact_shape(F, heads, {ldx, ldy, ldym}, &sh))) return st;
+    if ((st = exact_wide_ok(sh, A, nullptr, !self_col))) return st;
     const int32_t H = heads, D = F / H;
     std::vector<float> rc;
     if (!aR) {
@@ -1159,8 +1186,8 @@ extern "C" int gala_cpu_gat_fwd_stats_exact_ex_f32(const gala_csr_t *A, const fl
                 const float al = aL[r * H + h];
                 // one piece's edges into the state (a, am, m, sum, sm)
                 auto range = [&](int64_t e0, int64_t e1, float *a, float *am, float &m, float &sum, float &sm) {
-                    for (int64_t j0 = e0; j0 < e1; j0 += kExactU) {
-                        const int64_t j1 = std::min<int64_t>(j0 + kExactU, e1);
+                    for (int64_t j0 = e0; j0 < e1; j0 += sh.u) {
+                        const int64_t j1 = std::min<int64_t>(j0 + sh.u, e1);
                         float z[kExactU], mb = -INFINITY;
                         bool pos[kExactU];
                         for (int64_t e = j0; e < j1; ++e) {
@@ -1329,6 +1356,7 @@ extern "C" int gala_cpu_gat_bwd_exact_pre_ex_f32(const gala_csr_t *A, const floa
     if (!aL || !dY_rows || !lse || !Y || !Ym || !sma || !d_aL) return GALA_ERR_INVALID_ARG;
     ExactShape sh;
     if ((st = exact_shape(F, heads, {lddy, ldy, ldym}, &sh))) return st;
+    if ((st = exact_wide_ok(sh, A, nullptr, false))) return st;  // one pass alone: narrow rows only
     exact_pre_pass(A, sh, aL, dY_rows, lddy, F, heads, lse, Y, ldy, Ym, ldym, sma, self_col, side, d_aL);
     return GALA_OK;
 }
@@ -1346,6 +1374,7 @@ extern "C" int gala_cpu_gat_bwd_exact_gather_ex_f32(const gala_csr_t *A, const f
     if (!aR || !X || !dY || !dX || !d_aR) return GALA_ERR_INVALID_ARG;
     ExactShape sh;
     if ((st = exact_shape(F, heads, {ldx, lddy, lddx}, &sh))) return st;
+    if ((st = exact_wide_ok(sh, A, nullptr, false))) return st;
     exact_gather_pass(A, sh, aR, X, ldx, dY, lddy, F, heads, slope, side, self_col, dX, lddx, d_aR);
     return GALA_OK;
 }
@@ -1366,6 +1395,7 @@ extern "C" int gala_cpu_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float
     if (A->n_cols != A->n_rows) return GALA_ERR_INVALID_ARG;
     ExactShape sh;
     if ((st = exact_shape(F, heads, {ldx, lddy, ldy, ldym, lddx}, &sh))) return st;
+    if ((st = exact_wide_ok(sh, A, nullptr, true))) return st;
     exact_pre_pass(A, sh, aL, dY, lddy, F, heads, lse, Y, ldy, Ym, ldym, sma, nullptr, side, d_aL);
     exact_gather_pass(A, sh, aR, X, ldx, dY, lddy, F, heads, slope, side, nullptr, dX, lddx, d_aR);
     return GALA_OK;
@@ -1392,6 +1422,7 @@ extern "C" int gala_cpu_gat_bwd_stats_exact_t_f32(const gala_csr_t *A, const gal
     if (!aL || !aR || !X || !dY || !lse || !Y || !Ym || !sma || !dX || !d_aL || !d_aR) return GALA_ERR_INVALID_ARG;
     ExactShape sh;
     if ((st = exact_shape(F, heads, {ldx, lddy, ldy, ldym, lddx}, &sh))) return st;
+    if ((st = exact_wide_ok(sh, A, AT, true))) return st;
     exact_pre_pass(A, sh, aL, dY, lddy, F, heads, lse, Y, ldy, Ym, ldym, sma, nullptr, side, d_aL);
     exact_gather_pass(AT, sh, aR, X, ldx, dY, lddy, F, heads, slope, side, nullptr, dX, lddx, d_aR);
     return GALA_OK;

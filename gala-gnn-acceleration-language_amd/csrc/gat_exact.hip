@@ -21,20 +21,12 @@
 // the same gather kernels walk A^T (its own hub plan and workspace) after the pre-pass over
 // A's rows; gala_csr_is_transpose_i32 (csr_check.hip) is the test that the second pattern is
 // the first one's transpose.
-#include "gat_common.h"
+//
+// Rows of 257 .. 1024 floats (gat_wide_shape): the one-wave-per-row kernels of
+// gat_exact_wide.hip, through the same entry points; no hub rows, no _ex forms there.
+#include "gat_exact_wide.h"  // ExactDev
 
 namespace gala {
-
-// Operands the exact pair has beyond GatDev's.
-struct ExactDev {
-    float *lse_out;      // forward [n, H]
-    const float *lse;    // backward pre-pass [n, H]
-    float *side;         // backward: [n, H, 4] = {aL, lse, g, 0}
-    float *d_aR;         // backward [n, H]
-    // the column of each row's own vertex when the pattern's columns index gathered tables
-    // (X, aR, dY and side are then [n_cols, ...]); NULL: the row itself (square pattern)
-    const int32_t *self_col;
-};
 
 __device__ __forceinline__ int64_t own_col(const ExactDev &x, int64_t row) {
     return x.self_col ? (int64_t)x.self_col[row] : row;
@@ -487,6 +479,8 @@ struct ExactArgs {
     HubSplit sp;
     bool split, bwd;
     bool pre = true, gather = true;  // the backward's two passes (the _ex calls run one each)
+    const gala_csr_t *AT = nullptr;  // backward, nullable: the pattern the gather pass walks
+    EdgeParams pt;                   // AT's parameters (AT != NULL)
     hipStream_t hs;
 };
 
@@ -577,6 +571,16 @@ int exact_dispatch(const gala_csr_t *A, ExactArgs &a, int F, int heads, int vec,
     const int L = (F + vec - 1) / vec;
     const int ch = narrow_chunks(heads, vec, L);
     const int hw = (D % vec == 0) ? D / vec : 0;
+    // rows past 64 float4 vectors: the wide-row kernels (gat_exact_wide.hip), ahead of the
+    // ladders.  The forward and both backwards take one (F, heads, vec, plan) set: whole calls on
+    // a square pattern without hub rows (the gather's pattern too) -- no self_col, no dY_rows
+    // apart from dY, never one backward pass alone
+    if (L > 64 && gat_wide_shape(A, F, heads, vec) && (!a.AT || gat_wide_shape(a.AT, F, heads, vec))) {
+        if (a.x.self_col || (a.bwd && (a.d.dy_rows != a.d.dY || !a.pre || !a.gather))) return GALA_ERR_UNSUPPORTED;
+        if (rc && a.bwd) return GALA_ERR_INVALID_ARG;
+        if (!a.bwd) return gat_exact_wide_fwd(a.p, a.d, a.x, a.hs);
+        return gat_exact_wide_bwd(a.p, a.AT ? a.pt : a.p, a.d, a.x, a.hs);
+    }
     if (L > 64) return GALA_ERR_UNSUPPORTED;
     if (heads > 1 && (hw == 0 || (hw & (hw - 1)))) return GALA_ERR_UNSUPPORTED;
     if (plan_ws_short(A, ws_need)) return GALA_ERR_INVALID_ARG;
@@ -703,6 +707,12 @@ int exact_backward(const gala_csr_t *A, const gala_csr_t *AT, const ExactBwd &b,
     // the pre-pass is row-local: no hub chunks, no workspace
     const int64_t ws_need = gather ? 2 * (int64_t)F + heads : 0;
     if (!AT) return exact_dispatch(A, a, F, heads, vec, false, ws_need);
+    // rows past 64 vectors: one dispatch that sees both patterns' plans before it launches
+    // (served by the wide kernels, or refused whole)
+    if ((F + vec - 1) / vec > 64) {
+        a.AT = AT, a.pt = pt;
+        return exact_dispatch(A, a, F, heads, vec, false, 0);
+    }
     // the two passes apart, each over its own pattern, with the one vector width; AT's plan is
     // looked at before the pre-pass goes out, so a short workspace launches nothing.  "Nothing is
     // launched unless every check passed" rests on the two dispatches below sharing F, heads and

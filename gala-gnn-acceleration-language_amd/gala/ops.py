@@ -502,7 +502,9 @@ def gat_bwd_stats(g: DeviceGraph, aL, aR, dY, q, Y, Ym, sma, heads=1, slope=0.2,
 def gat_fwd_stats_exact(g: DeviceGraph, aL, X, aR=None, wR=None, bR=None, heads=1, slope=0.2):
     """gala_gat_fwd_stats_exact_f32 (the stable softmax, square pattern): returns (Y, lse, Ym, sma, aR)
     with lse[r, h] the log-sum-exp of the row's LeakyReLU'd logits and aR the source logits the
-    backward must read (the given aR, or the kernel's recompute from wR, bR)."""
+    backward must read (the given aR, or the kernel's recompute from wR, bR).  Rows of 256 < F <=
+    1024 floats are served too (float4 rows, F / heads a multiple of 4, at most 32 heads, a graph
+    without hub rows: DeviceGraph.from_host(g, split=False) or a plan that found none)."""
     F = X.shape[1]
     Y, Ym = _rows_like(X, g.n_rows), _rows_like(X, g.n_rows)
     lse = torch.empty(g.n_rows * heads, device=X.device, dtype=torch.float32)
@@ -518,7 +520,8 @@ def gat_bwd_stats_exact(g: DeviceGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads=1,
     """gala_gat_bwd_stats_exact_f32: the layer's true gradients (dX, d_aL, d_aR) from the forward's
     row statistics; aR as gat_fwd_stats_exact returned it.  The regrouping holds on a symmetric
     pattern only: symmetric=None tests g once (pattern_is_symmetric, kept on g), True is the
-    caller's assertion; anything else raises ValueError before a launch."""
+    caller's assertion; anything else raises ValueError before a launch.  Takes the wide rows
+    gat_fwd_stats_exact takes, and no others."""
     if symmetric is None:
         symmetric = pattern_is_symmetric(g)
     if not symmetric:
@@ -576,7 +579,8 @@ def gat_exact_directed(g: DeviceGraph, gT: DeviceGraph, aL, X, dY, aR=None, wR=N
 
 def gat_bwd_stats_exact_t(g: DeviceGraph, gT: DeviceGraph, aL, aR, X, dY, lse, Y, Ym, sma, heads=1, slope=0.2):
     """gala_gat_bwd_stats_exact_t_f32: (dX, d_aL, d_aR) from the forward's row statistics on g, the
-    gather pass over gT -- g's transpose, the caller's assertion (gat_exact_directed tests it)."""
+    gather pass over gT -- g's transpose, the caller's assertion (gat_exact_directed tests it).
+    Rows past 256 floats: neither g nor gT may have hub rows (as gat_exact_directed)."""
     F = dY.shape[1]
     dX = _rows_like(dY, g.n_rows)
     d_aL = torch.empty(g.n_rows * heads, device=dY.device, dtype=torch.float32)

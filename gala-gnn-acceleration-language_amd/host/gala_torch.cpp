@@ -913,15 +913,18 @@ GatGrads gat_backward(const torch::Tensor &l, torch::Tensor r, const torch::Tens
     return {daL, daR, dX};
 }
 
-// HIP backend only: past 256 floats per row only the row-statistics pair has a backward there
-// (gala_gat_bwd_ex_f32, gala_gat_bwd_fused_f32 and gala_sddmm_dot_f32 stay at 256), so a layer
-// on the device that needs gradients and did not take the pair is refused in its forward,
+// HIP backend only: past 256 floats per row only the row-statistics pairs have a backward there
+// (REF: gala_gat_{fwd,bwd}_stats_f32; FIXED: the exact pair on a symmetric pattern, or a directed
+// one under GALA_GAT_EXACT_DIRECTED=1; gala_gat_bwd_ex_f32, gala_gat_bwd_fused_f32 and
+// gala_sddmm_dot_f32 stay at 256), so a layer
+// on the device that needs gradients and did not take a pair is refused in its forward,
 // before any work, not in its backward.  The host-CPU backend has no width limit in these.
 void check_wide_has_backward(bool grad, const torch::Tensor &x) {
     const int64_t F = x.size(1);
     TORCH_CHECK(!grad || !x.is_cuda() || F <= 256, "gala: GAT layer failed: ",
                 gala_status_string(GALA_ERR_UNSUPPORTED),
-                " (rows of ", F, " floats have a backward only as a REF layer on one pattern without hub rows)");
+                " (rows of ", F, " floats have a backward only on patterns without hub rows: as a REF layer on "
+                "one pattern, or as a FIXED layer from row statistics on a symmetric pattern or a transposed pair)");
 }
 
 // One launch of the fused GAT forward (gala_gat_fwd_ex_f32) on slot 2li: aR, or its
@@ -1119,6 +1122,15 @@ bool exact_directed_layer(int64_t li, int64_t x_rows) {
     return tr;
 }
 
+// Past 256 floats per row the exact pair takes no hub rows, in the forward's pattern or in the
+// gather's: a directed layer whose transpose (slot 2li+1) has some is not served its forward
+// either, so no forward is served whose backward will be refused.
+bool exact_wide_transpose_ok(int64_t li, const torch::Tensor &x) {
+    if (x.size(1) <= 256) return true;
+    SplitState *sp = find_split(slot(2 * li + 1).off);
+    return !sp || sp->plan.n_rows_split == 0;
+}
+
 struct GatExact {
     torch::Tensor Y, lse, Ym, sma, aR;  // aR: the given logits, or the kernel's recompute
 };
@@ -1218,7 +1230,8 @@ struct GatAggregate : public torch::autograd::Function<GatAggregate> {
         GatExact ex;
         const bool fixed_grad = mode == GALA_SOFTMAX_FIXED && grad;
         const bool symm = fixed_grad && exact_stats_layer(li, x.size(0));
-        const bool directed = fixed_grad && !symm && exact_directed_layer(li, x.size(0));
+        const bool directed = fixed_grad && !symm && exact_directed_layer(li, x.size(0)) &&
+                              exact_wide_transpose_ok(li, x);
         if ((symm || directed) &&
             gat_forward_exact(s, l, r, x, {}, {}, heads, slope, ex)) {
             ctx->saved_data["exact"] = true;
@@ -1326,7 +1339,8 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
         GatExact ex;
         const bool fixed_grad = mode == GALA_SOFTMAX_FIXED && grad;
         const bool symm = fixed_grad && exact_stats_layer(li, x.size(0));
-        const bool directed = fixed_grad && !symm && exact_directed_layer(li, x.size(0));
+        const bool directed = fixed_grad && !symm && exact_directed_layer(li, x.size(0)) &&
+                              exact_wide_transpose_ok(li, x);
         if ((symm || directed) &&
             gat_forward_exact(s, l, {}, x, w, b, heads, slope, ex)) {
             // ex.aR: the recomputed source logits, the backward's second operand of every logit

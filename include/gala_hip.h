@@ -484,6 +484,12 @@ int gala_gat_bwd_stats_f32(const gala_csr_t *A, const float *aL, const float *aR
  * No atomics: results are bit-identical run to run.  Shapes as the REF statistics pair
  * (several heads need D/VEC a power of two, at most 64 vectors per row; else
  * GALA_ERR_UNSUPPORTED); a pattern that is not square is GALA_ERR_INVALID_ARG.
+ * Rows of 256 < F <= 1024 floats (csrc/gat_exact_wide.hip): float4-aligned operands and
+ * strides, D = F / heads a multiple of 4 (no power of two needed: 5 x 64, 2 x 384, one head of
+ * 260), at most 32 heads, one segment, and a plan without hub rows -- the same set for the
+ * forward and both backwards; anything else at this width, the _ex forms included, is
+ * GALA_ERR_UNSUPPORTED with nothing launched.  The rescale then comes every 8 edges at
+ * F <= 512 and every 4 past it, and head dots are summed in aligned lane groups.
  */
 int gala_gat_fwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *wR,
                                  const float *bR, const float *X, int64_t ldx, int32_t F, int32_t heads,
@@ -504,6 +510,8 @@ int gala_gat_bwd_stats_exact_f32(const gala_csr_t *A, const float *aL, const flo
  * square, single-segment, of the same n and nnz, else GALA_ERR_INVALID_ARG; so is an AT plan
  * with hub rows and a missing or smaller workspace; nothing is launched then.  With AT == A
  * (a symmetric pattern) the results are gala_gat_bwd_stats_exact_f32's bit for bit.
+ * Rows of 256 < F <= 1024 floats: as the pair above, and neither A's plan nor AT's may have
+ * hub rows (GALA_ERR_UNSUPPORTED, both looked at before the first launch).
  */
 int gala_gat_bwd_stats_exact_t_f32(const gala_csr_t *A, const gala_csr_t *AT, const float *aL, const float *aR,
                                    const float *X, int64_t ldx, const float *dY, int64_t lddy, int32_t F,
