@@ -5,6 +5,7 @@
 // Replaces the torch compositions around the emitted GAT kernels
 // (src/codegen/common.h:622-675, 735-810, 835-894; cuda.h:505-524, 679-734, 808-845).
 #include "gat_common.h"
+#include "gat_headw.h"
 #include "gat_wide.h"
 
 namespace gala {
@@ -914,6 +915,10 @@ static int gat_fwd_impl(const gala_csr_t *A, const float *aL, const float *aR, c
     // rows past 64 float4 vectors: the wide-row kernels (gat_wide.hip), ahead of the ladder
     if (gat_wide_shape(A, F, heads, vec) && !partial && !init_acc && !self_col)
         return gat_wide_fwd(a.p, a.d, a.mode, a.hs);
+    // head widths that are no power of two of float4 vectors (gat_headw.hip): the recomputed
+    // source logits and the row statistics, which the ladder's per-lane loop does not take
+    if (gat_headw_shape(A, F, heads, vec) && (rc || stats) && !partial && !init_acc && !self_col)
+        return gat_headw_fwd(a.p, a.d, a.mode, a.hs);
     // alpha of heads that do not divide the row group is formed by a per-head pass that
     // re-reads aR: there is none to read when it is recomputed
     if (rc && alpha_out && G % heads != 0) return GALA_ERR_UNSUPPORTED;

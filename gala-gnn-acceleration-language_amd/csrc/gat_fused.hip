@@ -16,6 +16,7 @@
 // partials and ordered fix-up).  d_aL's sums are taken per lane over the edges the lane
 // owns and combined at the end of the row: equal to the reference within fp32 rounding.
 #include "gat_common.h"
+#include "gat_headw.h"
 #include "gat_wide.h"
 
 namespace gala {
@@ -406,6 +407,8 @@ static int bwd_stats_impl(const gala_csr_t *A, const float *aL, const float *aR,
     a.split = hub_split(A, pad_to(F, 4), &a.sp);  // hub rows: dX[F] chunk partials
     // rows past 64 float4 vectors: the wide-row kernel (gat_wide.hip), ahead of the ladder
     if (gat_wide_shape(A, F, heads, vec) && !dY_rows) return gat_wide_bwd_stats(a.p, a.d, a.hs);
+    // head widths that are no power of two of float4 vectors (gat_headw.hip)
+    if (gat_headw_shape(A, F, heads, vec) && !dY_rows) return gat_headw_bwd_stats(a.p, a.d, a.hs);
     return fused_dispatch(a, F, heads, vec, false);
 }
 

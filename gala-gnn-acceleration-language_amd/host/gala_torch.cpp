@@ -927,6 +927,20 @@ void check_wide_has_backward(bool grad, const torch::Tensor &x) {
                 "one pattern, or as a FIXED layer from row statistics on a symmetric pattern or a transposed pair)");
 }
 
+// HIP backend only, the same for narrow rows whose heads are D / 4 float4 vectors wide with D / 4
+// no power of two (3 x 40, 8 x 24: csrc/gat_headw.hip): only the REF row-statistics pair on one
+// square pattern without hub rows has a backward there, so a layer that needs gradients and
+// did not take it (FIXED, REF on two patterns, GALA_GAT_ROWSTATS=0, a hub-row plan) is refused
+// in its forward.
+void check_head_width_has_backward(bool grad, const torch::Tensor &x, int heads) {
+    const int64_t F = x.size(1), D = F / heads;
+    const bool odd_width = heads > 1 && F <= 256 && D % 4 == 0 && ((D / 4) & (D / 4 - 1)) != 0;
+    TORCH_CHECK(!grad || !x.is_cuda() || !odd_width, "gala: GAT layer failed: ",
+                gala_status_string(GALA_ERR_UNSUPPORTED),
+                " (", heads, " heads of ", D, " floats have a backward only as a REF layer on one square pattern "
+                "without hub rows, from row statistics)");
+}
+
 // One launch of the fused GAT forward (gala_gat_fwd_ex_f32) on slot 2li: aR, or its
 // per-head recompute from x (wR, bR).  alpha / q as the entry point documents.
 torch::Tensor gat_forward_launch(const Slot &s, const torch::Tensor &l, const torch::Tensor &r,
@@ -1245,6 +1259,7 @@ struct GatAggregate : public torch::autograd::Function<GatAggregate> {
             return o.Y;
         }
         check_wide_has_backward(grad, x);
+        check_head_width_has_backward(grad, x, heads);
         auto alpha = recompute ? torch::empty({0}, fopts(x)) : torch::empty({s.cols.numel() * heads}, fopts(x));
         auto q = factored ? torch::empty({nrows * heads}, fopts(x)) : torch::empty({0}, fopts(x));
         auto Y = gat_forward_launch(s, l, r, x, {}, {}, heads, slope, mode,
@@ -1356,6 +1371,7 @@ struct GatAggregateFfn : public torch::autograd::Function<GatAggregateFfn> {
             return o.Y;
         }
         check_wide_has_backward(grad, x);
+        check_head_width_has_backward(grad, x, heads);
         auto alpha = recompute ? torch::empty({0}, fopts(x)) : torch::empty({s.cols.numel() * heads}, fopts(x));
         auto q = factored ? torch::empty({nrows * heads}, fopts(x)) : torch::empty({0}, fopts(x));
         auto Y = gat_forward_launch(s, l, {}, x, w, b, heads, slope, mode,

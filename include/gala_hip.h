@@ -321,6 +321,10 @@ int gala_edge_softmax_bwd_f32(const gala_csr_t *A, const float *alpha, const flo
  * 256 < F <= 1024, are served (csrc/gat_wide.hip) when D = F/heads is a multiple of 4,
  * heads <= 32, X / Y and their leading dimensions are 16-byte aligned, A is one segment and
  * its plan has no hub rows; anything else past 64 vectors is GALA_ERR_UNSUPPORTED.
+ * Head widths: with several heads the recomputed source logits (gala_gat_fwd_ex_f32 with wR)
+ * and the row-statistics pair need D / 4 a power of two, or (csrc/gat_headw.hip: 3 x 40, 8 x 24)
+ * D a multiple of 4, float4 operands, one segment, a square pattern and a plan without hub
+ * rows; other head widths are GALA_ERR_UNSUPPORTED there.
  */
 int gala_gat_fwd_f32(const gala_csr_t *A, const float *aL, const float *aR, const float *X,
                      int64_t ldx, int32_t F, int32_t heads, float slope, int32_t mode, float *Y,
