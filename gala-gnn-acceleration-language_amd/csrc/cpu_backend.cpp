@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/gala_cpu.h"
+#include "bf16.h"
 
 namespace {
 
@@ -64,6 +65,64 @@ extern "C" int gala_cpu_spmm_f32(const gala_csr_t *A, const float *X, int64_t ld
 // torch.relu as its GPU kernel computes it (the HIP backend's relu_t): t > 0 ? t : +0, NaN passes
 static inline float relu_t(float t) { return (t > 0.0f || t != t) ? t : 0.0f; }
 
+// GALA_SPMM_X_BF16 / GALA_SPMM_Y2_BF16 (after the fp32 call's argument checks): every gathered
+// element widened exactly, then the arithmetic of the fp32 loops below; Y2 rounded to bf16 with
+// the HIP library's helper.  The same served / refused set as libgala_hip.so.
+static int spmm_bf16_cpu(const gala_csr_t *A, const void *Xv, int64_t ldx, float *Y, int64_t ldy, int32_t F,
+                         const float *src_scale, const float *dst_scale, int32_t flags,
+                         const gala_spmm_epilogue_t *epi) {
+    const bool x_bf16 = (flags & GALA_SPMM_X_BF16) != 0, y2_bf16 = (flags & GALA_SPMM_Y2_BF16) != 0;
+    void *Y2 = epi ? (void *)epi->Y2 : nullptr;
+    if (y2_bf16 && !Y2) return GALA_ERR_INVALID_ARG;
+    const bool has_hubs = A->split && A->split->n_rows_split > 0;
+    if (A->n_seg != 1 || (flags & GALA_SPMM_SAMPLE) || (has_hubs && (flags & GALA_SPMM_HUB_CHUNKED)) ||
+        (epi && (epi->src_relu || epi->src_act || epi->relu_x)))
+        return GALA_ERR_UNSUPPORTED;
+    if (A->n_rows == 0 || F == 0) return GALA_OK;
+    if (!Y || (!Xv && A->nnz > 0)) return GALA_ERR_INVALID_ARG;
+    const bool w = A->val != nullptr;
+    if (w && (A->val_heads < 1 || F % A->val_heads != 0)) return GALA_ERR_INVALID_ARG;
+    if (A->val_row_scale && !w) return GALA_ERR_INVALID_ARG;
+    const int32_t H = w ? A->val_heads : 1, D = F / H;
+    const bool accum = (flags & GALA_SPMM_ACCUM) != 0, dst_deg = epi && epi->dst_deg_rsqrt;
+    const float *rs = A->val_row_scale, *y2s = Y2 ? epi->y2_scale : nullptr;
+    const int64_t ldy2 = Y2 ? epi->ldy2 : 0;
+    const uint16_t *Xh = static_cast<const uint16_t *>(Xv);
+    const float *Xf = static_cast<const float *>(Xv);
+#pragma omp parallel
+    {
+        std::vector<float> acc((size_t)F), xw((size_t)F);
+#pragma omp for schedule(dynamic, kRowChunk)
+        for (int64_t r = 0; r < A->n_rows; ++r) {
+            float *a = acc.data(), *x = xw.data(), *yr = Y + r * ldy;
+            for (int32_t f = 0; f < F; ++f) a[f] = (accum && !dst_scale && !dst_deg) ? yr[f] : 0.0f;
+            for (int64_t e = A->rowptr[r]; e < A->rowptr[r + 1]; ++e) {
+                const int64_t c = A->col[e];
+                for (int32_t f = 0; f < F; ++f) x[f] = x_bf16 ? gala::bf16_widen(Xh[c * ldx + f]) : Xf[c * ldx + f];
+                if (src_scale)
+                    for (int32_t f = 0; f < F; ++f) x[f] = src_scale[c] * x[f];
+                for (int32_t h = 0; h < H; ++h) {
+                    const float wv = !w ? 1.0f : rs ? A->val[e * H + h] * rs[r * H + h] : A->val[e * H + h];
+                    for (int32_t f = h * D; f < (h + 1) * D; ++f) a[f] = w ? fmaf(wv, x[f], a[f]) : a[f] + x[f];
+                }
+            }
+            const float ds = dst_deg ? 1.0f / sqrtf((float)(A->rowptr[r + 1] - A->rowptr[r]))
+                                     : (dst_scale ? dst_scale[r] : 1.0f);
+            for (int32_t f = 0; f < F; ++f)
+                yr[f] = !(dst_scale || dst_deg) ? a[f] : accum ? yr[f] + ds * a[f] : ds * a[f];
+            if (Y2) {
+                const float s2 = y2s ? y2s[r] : ds;
+                for (int32_t f = 0; f < F; ++f) {
+                    const float v = s2 * yr[f];
+                    if (y2_bf16) static_cast<uint16_t *>(Y2)[r * ldy2 + f] = gala::bf16_rne(v);
+                    else static_cast<float *>(Y2)[r * ldy2 + f] = v;
+                }
+            }
+        }
+    }
+    return GALA_OK;
+}
+
 // (every row is one sequential pass here: GALA_SPMM_HUB_CHUNKED is accepted and gives the
 // REF-order result, which is within that mode's tolerance)
 extern "C" int gala_cpu_spmm_ex_f32(const gala_csr_t *A, const float *X, int64_t ldx, float *Y,
@@ -73,7 +132,8 @@ extern "C" int gala_cpu_spmm_ex_f32(const gala_csr_t *A, const float *X, int64_t
     int st = check_csr(A);
     if (st) return st;
     if (F < 0 || ldx < F || ldy < F ||
-        (flags & ~(GALA_SPMM_ACCUM | GALA_SPMM_SAMPLE | GALA_SPMM_EXACT | GALA_SPMM_HUB_CHUNKED)) ||
+        (flags & ~(GALA_SPMM_ACCUM | GALA_SPMM_SAMPLE | GALA_SPMM_EXACT | GALA_SPMM_HUB_CHUNKED |
+                   GALA_SPMM_X_BF16 | GALA_SPMM_Y2_BF16)) ||
         ((flags & GALA_SPMM_EXACT) && (flags & GALA_SPMM_HUB_CHUNKED)))
         return GALA_ERR_INVALID_ARG;
     const bool dst_deg = epi && epi->dst_deg_rsqrt;
@@ -92,6 +152,8 @@ extern "C" int gala_cpu_spmm_ex_f32(const gala_csr_t *A, const float *X, int64_t
     if ((relu_pro || relu_x) &&
         (A->val || (flags & GALA_SPMM_SAMPLE) || Y2 || (A->split && A->split->n_rows_split > 0)))
         return GALA_ERR_UNSUPPORTED;
+    if (flags & (GALA_SPMM_X_BF16 | GALA_SPMM_Y2_BF16))
+        return spmm_bf16_cpu(A, X, ldx, Y, ldy, F, src_scale, dst_scale, flags, epi);
     if (A->n_rows == 0 || F == 0) return GALA_OK;
     if (!Y || (!X && A->nnz > 0)) return GALA_ERR_INVALID_ARG;
     const bool samp = (flags & GALA_SPMM_SAMPLE) != 0;

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "gala_internal.h"
+#include "spmm_bf16.h"
 
 namespace gala {
 
@@ -889,6 +890,119 @@ static int launch_vec(const SpmmParams &p, const SplitParams *sp, int L, bool w,
     return GALA_OK;
 }
 
+// ---- bf16 storage: GALA_SPMM_X_BF16 / GALA_SPMM_Y2_BF16 (kernels: csrc/spmm_bf16.hip) ----
+// Reached from gala_spmm_ex_f32 after its argument checks.  One segment, no sampling, no ReLU
+// fields, hub rows in REF order only; everything else of the fp32 call is served.
+static int spmm_bf16(const gala_csr_t *A, const void *X, int64_t ldx, float *Y, int64_t ldy, int32_t F,
+                     const float *src_scale, const float *dst_scale, int32_t flags,
+                     const gala_spmm_epilogue_t *epi, hipStream_t hs) {
+    const bool x_bf16 = (flags & GALA_SPMM_X_BF16) != 0, y2_bf16 = (flags & GALA_SPMM_Y2_BF16) != 0;
+    void *Y2 = epi ? (void *)epi->Y2 : nullptr;
+    if (y2_bf16 && !Y2) return GALA_ERR_INVALID_ARG;
+    const gala_split_plan_t *plan = A->split;
+    const bool has_hubs = plan && plan->n_rows_split > 0;
+    if (A->n_seg != 1 || (flags & GALA_SPMM_SAMPLE) || (has_hubs && (flags & GALA_SPMM_HUB_CHUNKED)) ||
+        (epi && (epi->src_relu || epi->src_act || epi->relu_x)))
+        return GALA_ERR_UNSUPPORTED;
+    if (A->n_rows == 0 || F == 0) return GALA_OK;
+    if (!Y || (!X && A->nnz > 0)) return GALA_ERR_INVALID_ARG;
+    const bool w = A->val != nullptr;
+    if (w && (A->val_heads < 1 || F % A->val_heads != 0)) return GALA_ERR_INVALID_ARG;
+    if (A->val_row_scale && !w) return GALA_ERR_INVALID_ARG;
+    const int32_t head_dim = w ? F / A->val_heads : F;
+    const int xv = bf16_pick_vec(x_bf16, X, ldx, Y, ldy, Y2, Y2 ? epi->ldy2 : 0, y2_bf16, F, head_dim,
+                                 !w || A->val_heads == 1);
+    const int64_t max_cols = (int64_t)kBf16MaxVecs * xv;  // wider rows: one launch per column range
+    // multi-head weights too narrow for the hub kernels' LDS staging (kHubMaxHeads per slice)
+    // keep their hub rows in the row kernel, as in the fp32 path
+    bool use_hub = has_hubs;
+    if (w && A->val_heads > 1) {
+        const int fsp = F <= 32 ? 32 : 64;
+        for (int f0 = 0; f0 < F; f0 += fsp) {
+            const int f1 = (f0 + fsp < F ? f0 + fsp : F) - 1;
+            if (f1 / head_dim - f0 / head_dim + 1 > kHubMaxHeads) use_hub = false;
+        }
+        if (!x_bf16 && F > max_cols) use_hub = false;  // k_spmm_hub_exact's heads count from column 0
+    }
+
+    Bf16Params p{};
+    p.rowptr = A->rowptr;
+    p.col = A->col;
+    p.val = A->val;
+    p.val_rs = A->val_row_scale;
+    p.src_scale = src_scale;
+    p.dst_scale = dst_scale;
+    p.n_rows = A->n_rows;
+    p.ldx = ldx;
+    p.ldy = ldy;
+    p.val_heads = w ? A->val_heads : 1;
+    p.head_dim = head_dim;
+    p.accum = (flags & GALA_SPMM_ACCUM) ? 1 : 0;
+    p.dst_deg = (epi && epi->dst_deg_rsqrt) ? 1 : 0;
+    p.ldy2 = Y2 ? epi->ldy2 : 0;
+    p.y2_scale = Y2 ? epi->y2_scale : nullptr;
+    p.y2_bf16 = y2_bf16 ? 1 : 0;
+    // the fp32 path's schedule: the plan's degree order when it has one, else XCD runs of row
+    // blocks (a block holds twice the fp32 kernel's rows, so a run covers twice the rows)
+    p.xcd_order = 1;
+    if (plan && plan->row_order) {
+        p.row_order = plan->row_order;
+        p.xcd_order = 0;
+    }
+    Bf16Hub hp{};
+    hipStream_t hub_st = hs;
+    if (use_hub) {
+        if (plan->threshold < 1 || !plan->rows) return GALA_ERR_INVALID_ARG;
+        p.split_threshold = plan->threshold;
+        hp.rows = plan->rows;
+        hp.order = plan->row_order;
+        hp.n_hub = plan->n_rows_split;
+        if (plan->aux_stream && plan->aux_events[0] && plan->aux_events[1]) hub_st = (hipStream_t)plan->aux_stream;
+    }
+    const bool forked = use_hub && hub_st != hs;
+    const size_t xs = x_bf16 ? 2 : 4, y2s = y2_bf16 ? 2 : 4;
+    for (int64_t c0 = 0; c0 < F; c0 += max_cols) {
+        Bf16Params q = p;
+        q.F = (int32_t)((F - c0) < max_cols ? (F - c0) : max_cols);
+        q.f_base = (int32_t)c0;
+        q.X = X ? (const char *)X + c0 * xs : nullptr;
+        q.Y = Y + c0;
+        q.Y2 = Y2 ? (char *)Y2 + c0 * y2s : nullptr;
+        int r = 0;
+        if (use_hub) {  // the long serial rows first, on the plan's side stream (fork / join as the fp32 path)
+            if (forked) {
+                if (hipEventRecord((hipEvent_t)plan->aux_events[0], hs) != hipSuccess ||
+                    hipStreamWaitEvent(hub_st, (hipEvent_t)plan->aux_events[0], 0) != hipSuccess)
+                    return launch_status();
+            }
+            if (x_bf16) {
+                r = bf16_launch_hub(q, hp, xv, hub_st);
+            } else {  // fp32 X, bf16 Y2: the fp32 hub kernel writes Y, then Y2 is rounded from it
+                SpmmParams h{};
+                h.rowptr = q.rowptr, h.col = q.col, h.val = q.val, h.val_rs = q.val_rs;
+                h.X = (const float *)q.X, h.Y = q.Y, h.src_scale = src_scale, h.dst_scale = dst_scale;
+                h.n_rows = q.n_rows, h.ldx = ldx, h.ldy = ldy, h.F = q.F;
+                h.val_heads = q.val_heads, h.head_dim = head_dim, h.accum = q.accum, h.dst_deg = q.dst_deg;
+                HubParams fh{};
+                fh.rows = hp.rows, fh.order = hp.order, fh.n_hub = hp.n_hub;
+                launch_hub(h, fh, xv, w, src_scale != nullptr, hub_st);
+                r = launch_status();
+                if (!r) r = bf16_launch_hub_y2(q, hp, hub_st);
+            }
+        }
+        if (!r) r = bf16_launch_rows(q, x_bf16, xv, hs);
+        if (forked) {  // join also after a failed launch, so a fork never stays open
+            if (hipEventRecord((hipEvent_t)plan->aux_events[1], hub_st) != hipSuccess ||
+                hipStreamWaitEvent(hs, (hipEvent_t)plan->aux_events[1], 0) != hipSuccess) {
+                const int j = launch_status();
+                if (!r) r = j ? j : GALA_ERR_HIP;
+            }
+        }
+        if (r) return r;
+    }
+    return GALA_OK;
+}
+
 }  // namespace gala
 
 using namespace gala;
@@ -922,9 +1036,12 @@ extern "C" int gala_spmm_ex_f32(const gala_csr_t *A, const float *X, int64_t ldx
     if (dst_deg && (dst_scale || A->n_seg != 1 || A->val || (flags & GALA_SPMM_SAMPLE))) return GALA_ERR_UNSUPPORTED;
     if (Y2 && ldy2 < F) return GALA_ERR_INVALID_ARG;
     if (F < 0 || ldx < F || ldy < F ||
-        (flags & ~(GALA_SPMM_ACCUM | GALA_SPMM_SAMPLE | GALA_SPMM_EXACT | GALA_SPMM_HUB_CHUNKED)) ||
+        (flags & ~(GALA_SPMM_ACCUM | GALA_SPMM_SAMPLE | GALA_SPMM_EXACT | GALA_SPMM_HUB_CHUNKED |
+                   GALA_SPMM_X_BF16 | GALA_SPMM_Y2_BF16)) ||
         ((flags & GALA_SPMM_EXACT) && (flags & GALA_SPMM_HUB_CHUNKED)))
         return GALA_ERR_INVALID_ARG;
+    if (flags & (GALA_SPMM_X_BF16 | GALA_SPMM_Y2_BF16))
+        return spmm_bf16(A, X, ldx, Y, ldy, F, src_scale, dst_scale, flags, epi, (hipStream_t)stream);
     if (A->n_rows == 0 || F == 0) return GALA_OK;
     if (!Y || (!X && A->nnz > 0)) return GALA_ERR_INVALID_ARG;
     const bool samp = (flags & GALA_SPMM_SAMPLE) != 0;

@@ -25,6 +25,23 @@ GALA_SPMM_ACCUM = 0x1
 GALA_SPMM_SAMPLE = 0x2
 GALA_SPMM_EXACT = 0x4
 GALA_SPMM_HUB_CHUNKED = 0x8
+GALA_SPMM_X_BF16 = 0x10    # X is bfloat16 storage (ldx in bf16 elements)
+GALA_SPMM_Y2_BF16 = 0x20   # the epilogue's Y2 is bfloat16 storage
+
+
+def spmm_storage_flags(X, out2=None) -> int:
+    """The SpMM's storage flags of its gathered operand X and its second output out2: fp32
+    (no flag) or bfloat16; any other dtype raises ValueError."""
+    flags = 0
+    for t, name, bit in ((X, "X", GALA_SPMM_X_BF16), (out2, "out2", GALA_SPMM_Y2_BF16)):
+        if t is None:
+            continue
+        dt = str(t.dtype)
+        if dt == "torch.bfloat16":
+            flags |= bit
+        elif dt != "torch.float32":
+            raise ValueError(f"spmm: {name} must be float32 or bfloat16, got {dt}")
+    return flags
 GALA_SDDVV_ADD = 0
 GALA_SDDVV_MUL = 1
 GALA_SDDVV_ADD_LRELU = 2

@@ -252,7 +252,8 @@ class CpuBackend:
         return CpuGraph(hg)
 
     def spmm(self, g: CpuGraph, X, out, dst_scale=None, accum=False, samp=None):
-        flags = (_abi.GALA_SPMM_ACCUM if accum else 0) | (_abi.GALA_SPMM_SAMPLE if samp is not None else 0)
+        flags = ((_abi.GALA_SPMM_ACCUM if accum else 0) | (_abi.GALA_SPMM_SAMPLE if samp is not None else 0)
+                 | _abi.spmm_storage_flags(X))   # a bf16 X is gathered as stored (GALA_SPMM_X_BF16)
         ns, ra, rb = samp if samp is not None else (0, 5, 7)
         _abi.call_cpu("gala_spmm_f32", g.csr(), _hp(X), X.stride(0), _hp(out), out.stride(0), X.shape[1],
                       None, _hp(dst_scale), flags, ns, ra, rb, None)
@@ -268,7 +269,7 @@ class CpuBackend:
         epi.dst_deg_rsqrt = 1
         epi.Y2, epi.ldy2, epi.y2_scale = _hp(out2), (out2.stride(0) if out2 is not None else 0), None
         _abi.call_cpu("gala_spmm_ex_f32", g.csr(), _hp(X), X.stride(0), _hp(out), out.stride(0), X.shape[1], None,
-                      None, 0, 0, 5, 7, ctypes.byref(epi), None)
+                      None, _abi.spmm_storage_flags(X, out2), 0, 5, 7, ctypes.byref(epi), None)
         return out
 
     def row_broadcast_deg(self, g: CpuGraph, X, out):

@@ -185,15 +185,22 @@ def spmm(g: DeviceGraph, X: torch.Tensor, src_scale=None, dst_scale=None, out=No
     prologue, gala_row_scale_relu_f32's roundings); relu_x -- the ReLU backward of the layer's
     input on the result, Y = relu_act * (relu(relu_act * relu_x) <= 0 ? 0 : Y)
     (gala_relu_scale_backward_f32's roundings).  The ReLU fields need an unweighted, unsampled
-    graph without hub rows (else GalaError UNSUPPORTED)."""
+    graph without hub rows (else GalaError UNSUPPORTED).
+
+    Storage: X may be torch.bfloat16 (GALA_SPMM_X_BF16) -- half the gathered bytes, every
+    element widened exactly and summed in fp32, so the result equals spmm(g, X.float(), ...)
+    bit for bit -- and out2 may be torch.bfloat16 (GALA_SPMM_Y2_BF16: rounded to nearest even,
+    the next layer's bf16 X).  out is always fp32.  One segment, no sampling, hub="exact", no
+    ReLU fields (else GalaError UNSUPPORTED); any other dtype raises ValueError."""
     F = X.shape[1]
+    storage = _abi.spmm_storage_flags(X, out2)
     if out is None:
-        out = _rows_like(X, g.n_rows, zero=accum)
+        out = _rows_like(X, g.n_rows, zero=accum)   # fp32 whatever X's dtype, with X's row padding
     if hub not in ("exact", "chunked"):
         raise ValueError(f"spmm: hub {hub!r} (exact | chunked)")
     chunked = hub == "chunked" and not exact
     flags = ((_abi.GALA_SPMM_ACCUM if accum else 0) | (_abi.GALA_SPMM_SAMPLE if nsamp is not None else 0)
-             | (_abi.GALA_SPMM_EXACT if exact else 0) | (_abi.GALA_SPMM_HUB_CHUNKED if chunked else 0))
+             | (_abi.GALA_SPMM_EXACT if exact else 0) | (_abi.GALA_SPMM_HUB_CHUNKED if chunked else 0) | storage)
     if dst_deg or out2 is not None or src_relu or relu_x is not None:
         epi = _abi.gala_spmm_epilogue_t()
         epi.dst_deg_rsqrt = int(bool(dst_deg))

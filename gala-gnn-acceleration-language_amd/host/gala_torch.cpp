@@ -274,11 +274,17 @@ torch::Tensor spmm_impl(const torch::Tensor &X, const torch::Tensor &offsets,
                         const torch::Tensor *src_scale, const torch::Tensor *dst_scale,
                         int64_t nsamples, int64_t ra, int64_t rb,
                         const torch::Tensor *val_row_scale = nullptr,
-                        const gala_spmm_epilogue_t *epi = nullptr) {
+                        const gala_spmm_epilogue_t *epi = nullptr, bool bf16_ok = false) {
+    // bf16 storage of the gathered operand (GALA_SPMM_X_BF16: widened exactly, summed and
+    // returned in fp32) is served by the non-autograd calls only; nothing is widened silently
+    const bool x_bf16 = X.defined() && X.scalar_type() == torch::kBFloat16;
+    TORCH_CHECK(!x_bf16 || bf16_ok,
+                "gala: input_dense is bfloat16, but the autograd Functions take float32; bf16 storage is served by "
+                "aggregate_node_mul_sum_call, aggregate_node_mul_sum_direct_call and gather_forward");
     if (!vals && nsamples == 0 && segments > 1 && offsets.is_cuda()) {
         if (const MergedCsr *m = find_merged(offsets))  // the same sums over one segment
             return spmm_impl(X, m->rowptr, m->col, nullptr, torch::Tensor(), 1, val_heads, src_scale, dst_scale, 0,
-                             ra, rb, nullptr, epi);
+                             ra, rb, nullptr, epi, bf16_ok);
     }
     CsrView cv = view(offsets, cols, vals, bounds, segments, val_heads);
     // the ReLU prologue / epilogue (gcn_aggregate_relu_apply) run on unweighted, unsampled
@@ -293,7 +299,7 @@ torch::Tensor spmm_impl(const torch::Tensor &X, const torch::Tensor &offsets,
     }
     const bool padded = row_padded(X);
     auto x = padded ? X : X.contiguous();
-    check_dev(x, torch::kFloat, "input_dense");
+    check_dev(x, x_bf16 ? torch::kBFloat16 : torch::kFloat, "input_dense");
     const int64_t nrows = cv.c.n_rows;
     // reference: dcols = input_dense.numel() / nrows (cuda.h:453-454)
     const int64_t dcols = x.dim() == 2 ? x.size(1) : x.numel() / std::max<int64_t>(nrows, 1);
@@ -317,11 +323,11 @@ torch::Tensor spmm_impl(const torch::Tensor &X, const torch::Tensor &offsets,
         check_dev(dsc, torch::kFloat, "dst_scale");
         ds = dsc.data_ptr<float>();
     }
-    const int32_t flags = nsamples > 0 ? GALA_SPMM_SAMPLE : spmm_hub_flag();
+    const int32_t flags = (nsamples > 0 ? GALA_SPMM_SAMPLE : spmm_hub_flag()) | (x_bf16 ? GALA_SPMM_X_BF16 : 0);
     check_on(x, offsets, "input_dense");
     if (ss) check_on(ssc, offsets, "src_scale");
     if (ds) check_on(dsc, offsets, "dst_scale");
-    check(be(offsets).spmm(&cv.c, x.data_ptr<float>(), ldx, out.data_ptr<float>(), ldy,
+    check(be(offsets).spmm(&cv.c, static_cast<const float *>(x.data_ptr()), ldx, out.data_ptr<float>(), ldy,
                            (int32_t)dcols, ss, ds, flags, (int32_t)nsamples, (int32_t)ra,
                            (int32_t)rb, epi, stream_of(offsets)),
           "gala_spmm_ex_f32");
@@ -500,7 +506,7 @@ torch::Tensor aggregate_node_mul_sum_call(torch::Tensor input_dense, torch::Tens
                                           torch::Tensor bounds, int64_t segments, bool weighted,
                                           int64_t nsamples, int64_t ra, int64_t rb) {
     return spmm_impl(input_dense, offset_graph, columns_graph, weighted ? &value_graph : nullptr,
-                     bounds, segments, 1, nullptr, nullptr, nsamples, ra, rb);
+                     bounds, segments, 1, nullptr, nullptr, nsamples, ra, rb, nullptr, nullptr, /*bf16_ok=*/true);
 }
 
 torch::Tensor aggregate_node_mul_sum_direct_call(torch::Tensor input_dense,

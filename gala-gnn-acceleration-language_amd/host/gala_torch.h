@@ -96,6 +96,9 @@ struct GraphSlots {
 GraphSlots &global_slots();
 
 // ---- emitted free functions ------------------------------------------------------------
+// aggregate_node_mul_sum_call, aggregate_node_mul_sum_direct_call and gather_forward also take a
+// torch::kBFloat16 input_dense on either device (GALA_SPMM_X_BF16: gathered as stored, widened
+// exactly, summed and returned in fp32).  The autograd Functions require fp32 and say so.
 torch::Tensor aggregate_node_mul_sum_call(torch::Tensor input_dense, torch::Tensor offset_graph,
                                           torch::Tensor columns_graph, torch::Tensor value_graph,
                                           torch::Tensor bounds = {}, int64_t segments = 1,

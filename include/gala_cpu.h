@@ -26,6 +26,9 @@
 extern "C" {
 #endif
 
+/* Both SpMM calls honour GALA_SPMM_X_BF16 (X carries the base address of a bfloat16 matrix, ldx in
+ * bf16 elements) and GALA_SPMM_Y2_BF16 (epi->Y2 likewise) as gala_spmm_f32 / gala_spmm_ex_f32 do:
+ * widened exactly, summed in fp32, the same served and refused cases. */
 int gala_cpu_spmm_f32(const gala_csr_t *A, const float *X, int64_t ldx, float *Y, int64_t ldy,
                       int32_t F, const float *src_scale, const float *dst_scale, int32_t flags,
                       int32_t nsamp, int32_t ra, int32_t rb, void *stream);

@@ -137,6 +137,8 @@ int gala_last_hip_error(void);                 /* hipError_t of the last GALA_ER
                                  kept as an explicit request; excludes HUB_CHUNKED)       */
 #define GALA_SPMM_HUB_CHUNKED 0x8 /* hub rows of A->split as chunk partials + ordered fix-up:
                                  the fast mode, within fp32 summation rounding of REF     */
+#define GALA_SPMM_X_BF16  0x10  /* X points at bfloat16 [n_cols, ldx]; ldx counted in bf16 elements        */
+#define GALA_SPMM_Y2_BF16 0x20  /* epi->Y2 points at bfloat16 [n_rows, ldy2]; ldy2 in bf16 elements; needs Y2 */
 
 /*
  * Y[r, 0:F] (+)= dst_scale[r] * sum_{e in row r} w_e * (src_scale[col_e] * X[col_e, 0:F])
@@ -154,6 +156,15 @@ int gala_last_hip_error(void);                 /* hipError_t of the last GALA_ER
  *           (cuda.h:286-436), the cuSPARSE "gather_forward" path (cuda.h:211-279),
  *           and the kernel-sampled variants (cuda.h:313-321,389-397).
  * ldx/ldy are row strides in elements (>= F).
+ *
+ * Opt-in bf16 storage of the gathered operand (GALA_SPMM_X_BF16): X keeps its declared type
+ * and carries the base address of a bfloat16 matrix [n_cols, ldx], ldx in bf16 elements; any
+ * F >= 1 and a base that is only 2-byte aligned are served.  Every element is widened exactly
+ * to fp32 and summed as above, so the result is bit-identical to this call on the widened
+ * matrix, at half the gathered bytes.  Y, the scales and the edge values stay fp32.  Served:
+ * one segment, weighted or not, src_scale / dst_scale, GALA_SPMM_ACCUM, GALA_SPMM_EXACT, a plan
+ * with a row order and / or hub rows in REF order.  GALA_ERR_UNSUPPORTED, before any launch:
+ * n_seg > 1, GALA_SPMM_SAMPLE, GALA_SPMM_HUB_CHUNKED on a plan with hub rows.
  */
 int gala_spmm_f32(const gala_csr_t *A, const float *X, int64_t ldx, float *Y, int64_t ldy,
                   int32_t F, const float *src_scale, const float *dst_scale, int32_t flags,
@@ -171,6 +182,12 @@ int gala_spmm_f32(const gala_csr_t *A, const float *X, int64_t ldx, float *Y, in
  *   Y2 != NULL:     also Y2[r, 0:F] = s2[r] * Y[r, 0:F] (s2 = y2_scale, or the dst factor
  *                   when NULL), rounded as the ROW_BROADCAST the next aggregation's input
  *                   would be -- bit-identical to that pass over Y.
+ * With GALA_SPMM_Y2_BF16 (with or without GALA_SPMM_X_BF16) the float *Y2 field carries the
+ * base address of a bfloat16 matrix [n_rows, ldy2], ldy2 in bf16 elements: s2 * Y is rounded to
+ * fp32 as above and then to bf16, nearest even (+-Inf stays, NaN becomes the quiet NaN 0x7FC0,
+ * as torch's conversion) -- the bf16 input of the next layer's GALA_SPMM_X_BF16 call.  Without
+ * Y2 the flag is GALA_ERR_INVALID_ARG.  Either bf16 flag with src_relu, src_act or relu_x is
+ * GALA_ERR_UNSUPPORTED, as are the cases listed at gala_spmm_f32.
  */
 typedef struct gala_spmm_epilogue {
     int32_t dst_deg_rsqrt;
