@@ -12,7 +12,7 @@ builder; a builder makes the operands on the device and returns a Built:
                The wrappers that allocate their outputs (sddvv, sddmm, edge_softmax, head_attn,
                edge_permute, the gat_fwd family, ...) stay: a launch of theirs on another stream
                shows through the NaN it reads from the poisoned inputs;
-    inputs     the float tensors the op reads (in-place operands included): the tests refill them;
+    inputs     the float (fp32 or bf16) tensors the op reads (in-place operands included): the tests refill them;
     outputs    a list the float (and the one int32) tensors the op wrote, refreshed by every run():
                fixed tensors where the op takes its outputs, the wrapper's fresh ones elsewhere;
     graphs     the DeviceGraphs whose hub-row plan owns a float workspace (an output as well);
@@ -580,6 +580,142 @@ def gat_in_q_scatter():
     return wrapped(lambda: ops.gat_in_q_scatter(L.xext, src, H, rows=rows), [L.xext, src])
 
 
+# ---- gat_wide.hip / gat_exact_wide.hip / gat_headw.hip / spmm_bf16.hip: kernel families behind the
+# ---- entry points above, reached by shape or storage ----------------------------------------------
+WIDE_SHAPE = (320, 5)    # rows past 256 floats, two 256-float slices per row (CH = 2): gat_wide_shape
+HEADW_SHAPE = (120, 3)   # a head of 10 float4 vectors, no power of two: gat_headw_shape
+BF16_F = 264             # scalar bf16 loads: two column ranges (256 + 8), two forks and joins on the plan's events
+
+
+def _family_graph(F, H):
+    """plain("cora"): both families refuse a plan with hub rows.  The kernels that served these
+    entry points before refuse both shapes (rows past 64 float4 vectors; a head width that is no
+    power of two of them), so a call that returns has run the new family."""
+    dg = plain("cora")
+    D4 = F // H // 4
+    assert dg.split_rows == 0 and dg.n_rows == dg.n_cols and F % (4 * H) == 0
+    assert (256 < F <= 1024 and H <= 32) or (F <= 256 and H > 1 and D4 & (D4 - 1))
+    return dg
+
+
+def _family_fwd_ex(shape, seed):
+    F, H = shape
+    dg = _family_graph(F, H)
+    aL, _, X, _ = _gat_operands(dg, F, H, seed)
+    wR, bR = rnd(seed + 4, F), rnd(seed + 5, H)
+    return wrapped(lambda: ops.gat_fwd_ex(dg, aL, X, wR=wR, bR=bR, heads=H, factored=True), [aL, wR, bR, X])
+
+
+def _family_fwd_stats(shape, seed):
+    F, H = shape
+    dg = _family_graph(F, H)
+    aL, _, X, _ = _gat_operands(dg, F, H, seed)
+    wR, bR = rnd(seed + 4, F), rnd(seed + 5, H)
+    return wrapped(lambda: ops.gat_fwd_stats(dg, aL, X, wR=wR, bR=bR, heads=H, want_aR=True, want_p=True), [aL, wR, bR, X])
+
+
+def _family_bwd_stats(shape, seed, linear):
+    """linear: gala_gat_bwd_stats_linear_f32 without dY_rows, the form bwd_stats_impl hands to both
+    families (csrc/gat_fused.hip:409-411; with dY_rows it takes the old ladder)."""
+    F, H = shape
+    dg = _family_graph(F, H)
+    a = _stats(dg, F, H, seed)
+    if not linear:
+        return wrapped(lambda: ops.gat_bwd_stats(dg, *a, heads=H), a)
+    wR = rnd(seed + 4, F)
+    return wrapped(lambda: ops.gat_bwd_stats(dg, *a, heads=H, wR=wR), a + (wR,))
+
+
+def gat_fwd_ex_wide():
+    """k_gat_wide_fwd<2, REF, recomputed logits> through launch_wide (csrc/gat_wide_lanes.h)."""
+    return _family_fwd_ex(WIDE_SHAPE, 300)
+
+
+def gat_fwd_stats_wide():
+    """k_gat_wide_fwd<2, kRefStats, recomputed logits>."""
+    return _family_fwd_stats(WIDE_SHAPE, 310)
+
+
+def gat_bwd_stats_wide():
+    """k_gat_wide_bwd_stats<2, from aR>."""
+    return _family_bwd_stats(WIDE_SHAPE, 320, False)
+
+
+def gat_bwd_stats_linear_wide():
+    """k_gat_wide_bwd_stats<2, from aR> with attn_w: dX also takes d_aL * wR at the store."""
+    return _family_bwd_stats(WIDE_SHAPE, 330, True)
+
+
+def gat_fwd_stats_exact_wide():
+    """k_gat_exact_wide_fwd<2, recomputed logits>."""
+    F, H = WIDE_SHAPE
+    dg = _family_graph(F, H)
+    aL, _, X, _ = _gat_operands(dg, F, H, 340)
+    wR, bR = rnd(344, F), rnd(345, H)
+    return wrapped(lambda: ops.gat_fwd_stats_exact(dg, aL, X, wR=wR, bR=bR, heads=H), [aL, wR, bR, X])
+
+
+def gat_bwd_stats_exact_wide():
+    """k_gat_exact_wide_bwd_pre<2> then k_gat_exact_wide_bwd<2>: two dependent launches on the
+    caller's stream (csrc/gat_exact_wide.hip: exact_wide_bwd_ch), on the symmetric cora graph."""
+    F, H = WIDE_SHAPE
+    g = _family_graph(F, H)
+    return _bwd_exact("gala_gat_bwd_stats_exact_f32", (g,), g, F, H, 350)
+
+
+def gat_fwd_ex_headw():
+    """k_gat_headw_fwd<G, REF, recomputed logits> through launch_headw (csrc/gat_headw.hip)."""
+    return _family_fwd_ex(HEADW_SHAPE, 360)
+
+
+def gat_fwd_stats_headw():
+    """k_gat_headw_fwd<G, kRefStats, recomputed logits>."""
+    return _family_fwd_stats(HEADW_SHAPE, 370)
+
+
+def gat_bwd_stats_headw():
+    """k_gat_headw_bwd_stats<G, from aR>."""
+    return _family_bwd_stats(HEADW_SHAPE, 380, False)
+
+
+def gat_bwd_stats_linear_headw():
+    """k_gat_headw_bwd_stats<G, from aR> with attn_w."""
+    return _family_bwd_stats(HEADW_SHAPE, 390, True)
+
+
+def _bf16_x(seed, n, F):
+    """A bf16 [n, F] view whose base is 2-byte aligned only: bf16_pick_vec falls to scalar loads."""
+    X = rnd(seed, n, F + 2).to(torch.bfloat16)[:, 1:F + 1]
+    assert X.dtype == torch.bfloat16 and X.data_ptr() % 4 == 2 and F > 256
+    return X
+
+
+def spmm_bf16():
+    """spmm_bf16() (csrc/spmm.hip) on bf16 X: per column range a fork, k_spmm_bf16_hub<1, FSP> on the
+    plan's side stream, k_spmm_bf16_rows<bf16, 1> on the caller's and a join -- twice, on one pair of events."""
+    dg, F = hub(), BF16_F
+    X, ss, ds = _bf16_x(400, dg.n_cols, F), rnd(401, dg.n_cols), rnd(402, dg.n_rows)
+    out = empty(dg.n_rows, F)
+    return wrapped(lambda: ops.spmm(dg, X, src_scale=ss, dst_scale=ds, out=out), [X, ss, ds], [dg])
+
+
+def spmm_ex_bf16_y2():
+    """fp32 X, bf16 out2: k_spmm_hub_exact then k_spmm_bf16_hub_y2 chained on the side stream beside
+    k_spmm_bf16_rows<float>."""
+    dg, F = hub(), 32
+    X, ss = rnd(403, dg.n_cols, F), rnd(404, dg.n_cols)
+    out, out2 = empty(dg.n_rows, F), torch.empty(dg.n_rows, F, device="cuda", dtype=torch.bfloat16)
+    return wrapped(lambda: (ops.spmm(dg, X, src_scale=ss, out=out, dst_deg=True, out2=out2), out2), [X, ss], [dg])
+
+
+def spmm_ex_bf16_both():
+    """bf16 X and bf16 out2 over two column ranges: k_spmm_bf16_hub and k_spmm_bf16_rows round Y2 themselves."""
+    dg, F = hub(), BF16_F
+    X, ss = _bf16_x(405, dg.n_cols, F), rnd(406, dg.n_cols)
+    out, out2 = empty(dg.n_rows, F), torch.empty(dg.n_rows, F, device="cuda", dtype=torch.bfloat16)
+    return wrapped(lambda: (ops.spmm(dg, X, src_scale=ss, out=out, dst_deg=True, out2=out2), out2), [X, ss], [dg])
+
+
 CASES = {
     "gala_spmm_f32": spmm,
     "gala_spmm_ex_f32": spmm_ex,
@@ -637,6 +773,23 @@ CASES = {
 # further cases of an entry point that has one above: paths its first case does not reach
 EXTRA_CASES = {
     "gala_dense_grad_f32-n0": dense_grad_empty,
+    # The kernel families that arrived behind existing entry points (each builder's docstring names
+    # its kernel).  gala_gat_bwd_stats_linear_f32 reaches the wide and head-width kernels when it is
+    # called without dY_rows (csrc/gat_fused.hip:409-411), so both have a -linear case; the _ex entry
+    # points (self_col, dY_rows) never reach them and have none.
+    "gala_gat_fwd_ex_f32-wide": gat_fwd_ex_wide,
+    "gala_gat_fwd_stats_f32-wide": gat_fwd_stats_wide,
+    "gala_gat_bwd_stats_f32-wide": gat_bwd_stats_wide,
+    "gala_gat_bwd_stats_linear_f32-wide": gat_bwd_stats_linear_wide,
+    "gala_gat_fwd_stats_exact_f32-wide": gat_fwd_stats_exact_wide,
+    "gala_gat_bwd_stats_exact_f32-wide": gat_bwd_stats_exact_wide,
+    "gala_gat_fwd_ex_f32-headw": gat_fwd_ex_headw,
+    "gala_gat_fwd_stats_f32-headw": gat_fwd_stats_headw,
+    "gala_gat_bwd_stats_f32-headw": gat_bwd_stats_headw,
+    "gala_gat_bwd_stats_linear_f32-headw": gat_bwd_stats_linear_headw,
+    "gala_spmm_f32-bf16": spmm_bf16,
+    "gala_spmm_ex_f32-bf16y2": spmm_ex_bf16_y2,
+    "gala_spmm_ex_f32-bf16both": spmm_ex_bf16_both,
 }
 ALL_CASES = {**CASES, **EXTRA_CASES}
 

@@ -6,7 +6,8 @@ caller enqueued on that stream before the call and before what it enqueues after
 synchronisation and no allocation inside.  The other GPU tests call the library on the default
 stream and synchronise, where a launch on stream 0, a missing fork or join, or a buffer that is
 valid only the first time are all invisible.  The cases are tests/_stream_cases.py's, one per
-entry point; the numbers are the other tests' business, only their order is checked here.
+entry point and one more per kernel family that an entry point reaches by shape or storage; the
+numbers are the other tests' business, only their order is checked here.
 
 Delayed producer, poisoned consumer (test_side_stream_order): the reference is the op on the
 default stream.  Then every float operand is NaN; on a side stream a delay, an event, NaN fills of
@@ -31,6 +32,17 @@ memsets on stream 0 (both tests of gala_dense_grad_f32-n0), row_sum's HubFork::j
 tests of gala_row_sum_f32), the fork of spmm's hub launch dropped (both tests of gala_spmm_f32 and
 gala_spmm_ex_f32).  gat_in_bwd's memset of M on stream 0 changes nothing a caller can see:
 k_gat_in_reduce stores every element of M afterwards.
+
+The kernel families behind existing entry points (the -wide, -headw and -bf16 cases of EXTRA_CASES),
+likewise one change at a time: stream 0 in launch_wide (csrc/gat_wide_lanes.h) turns
+test_capture_and_replay red for all six -wide cases and test_side_stream_order for five of them
+(gala_gat_fwd_ex_f32-wide passed in that run); the bf16 SpMM's join after the last column range
+dropped (spmm_bf16() in csrc/spmm.hip) turns both tests of gala_spmm_f32-bf16,
+gala_spmm_ex_f32-bf16y2 and gala_spmm_ex_f32-bf16both red.  The fork before the second column
+range's hub launch dropped (the launch stays on the plan's side stream) changes nothing a caller can
+see and every test stays green: the side stream is in order and already waits for the first range's
+fork, and the second range's hub launch shares no column with the first range's row kernel, the
+one thing the second fork orders it after.
 """
 import time
 
@@ -98,7 +110,10 @@ def poison(ts):
 
 
 def bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
+    """Floats by their bits (fp32 as int32, bf16 as int16): a NaN equals itself."""
+    if t.dtype == torch.float32:
+        return t.contiguous().view(torch.int32)
+    return t.contiguous().view(torch.int16) if t.dtype == torch.bfloat16 else t
 
 
 def same(got, want, name):
@@ -110,9 +125,9 @@ def same(got, want, name):
 
 
 def perturbed(stage, seed):
-    """New inputs of the same signs and magnitudes (factors in [0.5, 1.5))."""
+    """New inputs of the same signs, magnitudes and storage (factors in [0.5, 1.5))."""
     gen = torch.Generator(device="cuda").manual_seed(seed)
-    return [s * (0.5 + torch.rand(s.shape, device="cuda", generator=gen)) for s in stage]
+    return [(s * (0.5 + torch.rand(s.shape, device="cuda", generator=gen))).to(s.dtype) for s in stage]
 
 
 def load(inputs, values):
